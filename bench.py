@@ -29,6 +29,7 @@ Extra objects on that line:
   devices_distinct, devices, per_rank_ms_per_step   what the ranks computed on (PCI address / UUID of every rank's device)
   sampling_chain, kinds, latency_one_scene, with_fp, config5   the chain's identity share per level; the same step on the other
                 input families (uniform box, padded with exact twins, decimal-quantised); further verified measurements
+  dumped_outputs  (--dump-outputs DIR) the arrays written to DIR: what the last timed step completed, for comparing two builds
 """
 import argparse
 import json
@@ -86,6 +87,10 @@ def parse():
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow EPNET_BENCH_DEVICE / EPNET_BENCH_BACKEND (all ranks on one device, gloo instead of RCCL): the line "
                          "then says rehearsal: true and its devices_distinct shows it; without the flag both variables are refused")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them completed (centres, ball-query indices, grouped tensors "
+                         "and, with --with-fp, the FP outputs of one batch) as DIR/<name>.npy, float32, at most 64 MB in all: a larger "
+                         "array is replaced by a fixed seeded sample of its elements (rank 0; the line lists what was written)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rehearse the N-rank launch only: the ranks rendezvous (backend EPNET_BENCH_BACKEND, default nccl), "
                          "count themselves with an all-reduce and rank 0 prints n_gpus / ranks_seen; no kernels of the path")
@@ -286,6 +291,64 @@ def verify_scene(stack, xyz, scene, prev_xyz=None, prev2_xyz=None):
         want = oracle.three_interpolate(F["known_feats"][scene:scene + 1].cpu().numpy(), nn_idx, weight)
         same(tag + "three_interpolate", F["out"][scene:scene + 1], want, tol=1e-5)
     return bad
+
+
+DUMP_BYTES = 63 << 20   # --dump-outputs: the data of all arrays together (float32), leaving room for the .npy headers under 64 MB
+
+
+def completed_outputs(stack):
+    """What the caller of the SA stack receives for the batch whose processing the last step finished, by name: per level the
+    centres, per scale the ball-query indices and the grouped tensor, and (--with-fp) the FP neighbour search and interpolation.
+    A pipelined step finishes the batch its stage G grouped (SAStack.owners() / owners3()); an unpipelined step its own."""
+    g = stack.owners3()[2] if stack.stages == 3 else stack.owners()[1]
+    out = {}
+    for lvl, L in enumerate(stack.levels):
+        tag = "level%d." % (lvl + 1)
+        out[tag + "centres"] = L["sets"][g]["new_xyz"]
+        for S in L["scales"]:
+            stag = tag + "r%g." % S["radius"]
+            idx_sets = S.get("idx_sets", [S["idx"]])
+            out[stag + "ball_idx"] = idx_sets[g] if len(idx_sets) > 1 else S["idx"]
+            if stack.fused:
+                out[stag + "grouped"] = S["grouped"]
+            else:
+                out[stag + "grouped_xyz"] = S["grouped_xyz"]
+                if S["grouped_feat"] is not None:
+                    out[stag + "grouped_feat"] = S["grouped_feat"]
+    for k, F in enumerate(stack.fp_bufs if stack.with_fp else []):
+        tag = "fp%d." % (len(stack.levels) - k)
+        P = F["sets"][g] if len(F["sets"]) > 1 else F["sets"][0]
+        out[tag + "three_nn_idx"] = P["idx"]
+        out[tag + "three_nn_dist2"] = P["dist2"]
+        out[tag + "three_interpolate"] = F["out"]
+    return out
+
+
+def dump_outputs(arrays, directory, budget=DUMP_BYTES):
+    """writes every tensor as <directory>/<name>.npy in float32 (the indices are < 2^24: exact). An array larger than its share
+    of `budget` is replaced by a fixed sample of its elements: sorted flat positions drawn from a generator seeded by the
+    array's name and size, so that two runs with the same arguments sample the same positions. Returns name -> shape / sampled."""
+    import zlib
+
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    share = budget // (4 * max(1, len(arrays)))
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if t.dtype in (torch.int32, torch.int64):
+            assert int(flat.abs().max()) < (1 << 24), (name, "indices beyond float32's exact range")
+        sampled = None
+        if flat.numel() > share:
+            rng = np.random.default_rng(zlib.crc32(("%s %d" % (name, flat.numel())).encode()))
+            pos = np.sort(rng.choice(flat.numel(), size=share, replace=False))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+            sampled = share
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a if sampled else a.reshape(tuple(t.shape)))
+        info[name] = {"shape": list(t.shape), "sampled": sampled}
+    return info
 
 
 class OpTimer:
@@ -555,6 +618,10 @@ def main():
         return {"ms_per_step_min": round(ms[0], 4), "ms_per_step_median": round(ms[len(ms) // 2], 4), "ms_per_step_max": round(ms[-1], 4)}
 
     elapsed, stack, batches, step = time_stack(args.batch, args.steps, args.warmup)
+    dumped = None
+    if rank == 0 and args.dump_outputs:   # before anything else steps the stack again
+        torch.cuda.synchronize()
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(completed_outputs(stack), args.dump_outputs)}
     xyz = batches[0]
     stack_s_levels, stack_chain, stack_stages = stack.s_query_levels, stack.chain, stack.stages
     reduce_dev = dev if dist.is_initialized() and dist.get_backend() == "nccl" else "cpu"
@@ -738,6 +805,8 @@ def main():
                                        "level's sample count takes idx = 0..m-1 without running rounds (epnet_sample_centres_chain)"},
         }
         line.update(spread)
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world > 1:
             line["cpu_baseline_note"] = "the CPU baseline is timed in the N = 1 run only (rank 0 there has the host to itself)"
         if sweep:

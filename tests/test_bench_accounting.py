@@ -66,3 +66,27 @@ def test_dominant_family_is_stable_when_sampling_and_grouping_trade_places():
     assert bench.pick_dominant(k) == ("group", "group")
     k["group"] = fam(1.2, 4, 3_100_000_000)                   # far behind: the longest family is named, whatever it moves
     assert bench.pick_dominant(k) == ("fps N=16384 M=4096", "fps N=16384 M=4096")
+
+
+def test_dump_outputs_is_float32_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: every array as float32 .npy; the large ones replaced by the same seeded sample of their elements from run
+    to run, the whole under the budget"""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"level1.centres": torch.arange(2 * 8 * 3, dtype=torch.float32).reshape(2, 8, 3),
+              "level1.r0.1.ball_idx": torch.arange(4 * 1000 * 16, dtype=torch.int32).reshape(4, 1000, 16) % 16384,
+              "level1.r0.1.grouped": torch.randn((4, 3, 1000, 16), generator=torch.Generator().manual_seed(0))}
+    budget = 3 * 4 * 20000
+    info = [bench.dump_outputs(arrays, str(tmp_path / d), budget=budget) for d in ("a", "b")]
+    assert info[0] == info[1] and info[0]["level1.centres"]["sampled"] is None and info[0]["level1.r0.1.grouped"]["sampled"] == 20000
+    total = 0
+    for name, t in arrays.items():
+        a, b = (np.load(str(tmp_path / d / (name + ".npy"))) for d in ("a", "b"))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += a.nbytes
+        if info[0][name]["sampled"] is None:
+            assert np.array_equal(a, t.float().numpy())
+        else:   # a sample of the array's own values, in the order of their positions
+            assert a.size == info[0][name]["sampled"] and np.isin(a, t.float().numpy().ravel()).all()
+    assert total <= budget

@@ -1,10 +1,9 @@
-"""The oracle against (i) the reference's own compiled roipool3d CPU ops -- live when /root/reference is
-present, and through the committed fixture captured from that build everywhere -- and (iii) against the
-fixtures captured by running the reference's Python surface (tests/golden/make_golden.py)."""
+"""The oracle against (i) the reference's own compiled roipool3d CPU ops -- through the committed fixtures captured from that
+build everywhere, and live where the build is at hand -- and (iii) against the fixtures captured by running the reference's
+Python surface (tests/golden/make_golden.py)."""
 import os
 
 import numpy as np
-import pytest
 
 from conftest import golden
 
@@ -25,29 +24,33 @@ def test_roipool3d_fixture_from_reference_build(oracle):
     np.testing.assert_array_equal(pooled[0, :, :, 3:], fx["pooled_features"])
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/lib/utils/roipool3d/src/roipool3d.cpp"),
-                    reason="reference checkout not present (GPU box)")
 def test_oracle_vs_live_reference_build(oracle):
+    """three random scenes through the reference's compiled ops, stored by tests/golden/make_golden_roipool3d_trials.py; where
+    that build is at hand (oracle/_ref/), it runs again live on the same inputs"""
     import torch
     from oracle import build_ref
-    ref = build_ref.load()
-    rng = np.random.default_rng(3)
+    fx = golden("roipool3d_ref_trials.npz")
+    ref = build_ref.load() if (os.path.exists(build_ref.OUT) or build_ref.available()) else None
     for trial in range(3):
-        n, m, c, s = 3000 + 500 * trial, 24, 4 + trial, 48
-        pts = (rng.random((n, 3)) * [30, 4, 30] - [15, 1, 0]).astype(np.float32)
-        boxes = np.stack([rng.uniform(-15, 15, m), rng.uniform(0, 3, m), rng.uniform(0, 30, m), rng.uniform(1, 3, m),
-                          rng.uniform(1, 5, m), rng.uniform(2, 9, m), rng.uniform(-4, 4, m)], 1).astype(np.float32)
-        feat = rng.standard_normal((n, c)).astype(np.float32)
-        flag = torch.zeros((m, n), dtype=torch.int64)
-        ref.pts_in_boxes3d_cpu(flag, torch.from_numpy(pts), torch.from_numpy(boxes))
-        np.testing.assert_array_equal(flag.numpy(), oracle.pts_in_boxes3d(pts, boxes))
+        pts, boxes, feat = fx["pts_%d" % trial], fx["boxes3d_%d" % trial], fx["pts_feature_%d" % trial]
+        m, n, c, s = boxes.shape[0], pts.shape[0], feat.shape[1], fx["pooled_pts_%d" % trial].shape[1]
+        flag = np.unpackbits(fx["pts_flag_%d" % trial], axis=1)[:, :n].astype(np.int64)
+        pp, pf, ef = fx["pooled_pts_%d" % trial], fx["pooled_features_%d" % trial], fx["pooled_empty_flag_%d" % trial]
+        if ref is not None:
+            live = torch.zeros((m, n), dtype=torch.int64)
+            ref.pts_in_boxes3d_cpu(live, torch.from_numpy(pts), torch.from_numpy(boxes))
+            np.testing.assert_array_equal(live.numpy(), flag)
+            lp, lf, le = torch.zeros((m, s, 3)), torch.zeros((m, s, c)), torch.zeros(m, dtype=torch.int64)
+            ref.roipool3d_cpu(torch.from_numpy(pts), torch.from_numpy(boxes), torch.from_numpy(feat), lp, lf, le)
+            np.testing.assert_array_equal(lp.numpy(), pp)
+            np.testing.assert_array_equal(lf.numpy(), pf)
+            np.testing.assert_array_equal(le.numpy(), ef)
+        np.testing.assert_array_equal(flag, oracle.pts_in_boxes3d(pts, boxes))
         assert flag.sum() > 0
-        pp, pf, ef = torch.zeros((m, s, 3)), torch.zeros((m, s, c)), torch.zeros(m, dtype=torch.int64)
-        ref.roipool3d_cpu(torch.from_numpy(pts), torch.from_numpy(boxes), torch.from_numpy(feat), pp, pf, ef)
         a, b, e = oracle.roipool3d_cpu(pts, boxes, feat, s)
-        np.testing.assert_array_equal(pp.numpy(), a)
-        np.testing.assert_array_equal(pf.numpy(), b)
-        np.testing.assert_array_equal(ef.numpy(), e)
+        np.testing.assert_array_equal(pp, a)
+        np.testing.assert_array_equal(pf, b)
+        np.testing.assert_array_equal(ef, e)
 
 
 def test_cfg1_fixture(oracle):
