@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SA-stack points/s per GPU on synthetic KITTI-shaped scenes (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--pipelined 0|1] [--kind kitti|ubox|dup|kitti_q] [--no-graph]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--pipelined 0|1] [--kind kitti|ubox|dup|kitti_q] [--no-graph] [--full]
 
 One "step" = one pass of the 4-level set-abstraction OPERATOR stack (per level: scene index, sampling [FPS + centre gather; levels
 2-4 nested in level 1 where tie-free], two ball queries, two fused groupings -- epnet_amd/sa_stack.py) over a batch of B independent
@@ -14,7 +14,10 @@ torch.distributed.run, one rank per GPU; every rank owns its own scenes (differe
 (the ops are independent per scene), so scaling is "weak". Timing: barrier + synchronize on both sides of exactly K steps, MAX over
 ranks; rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs if asked and prints
+the line (value, ms_per_step, the configuration, what every rank ran on). It neither checks nor measures anything else, and does
+not load the CPU oracle. --full adds these objects to the line, measured as before (the CPU baselines before the process touches
+the GPU, the rest after the timed steps):
   roofline      the op family with the largest share of the step (pick_dominant: among families within 10 % of the longest the
                 one that moves the most bytes -- the level-1 sampling's chain of rounds and the grouping calls are 2.1 - 2.2 ms each
                 and trade places from run to run; `dominant_by_time` names the longest of this run), priced by its ALGORITHMIC
@@ -26,9 +29,11 @@ Extra objects on that line:
   verified      scene 0 of the buffers the timed steps left behind, every tensor against the oracle, each resident batch in each
                 role (verification.distinct_inputs).
   ms_per_step_min / _median / _max   per-step durations from an event pair around every step (a loop of its own after the timed one)
-  devices_distinct, devices, per_rank_ms_per_step   what the ranks computed on (PCI address / UUID of every rank's device)
   sampling_chain, kinds, latency_one_scene, with_fp, config5   the chain's identity share per level; the same step on the other
                 input families (uniform box, padded with exact twins, decimal-quantised); further verified measurements
+  device_copy_GBps, stack_frac_of_device_copy, sweep   a plain 2 GiB device copy; --sweep's batch sizes
+Both kinds of run carry:
+  devices_distinct, devices, per_rank_ms_per_step   what the ranks computed on (PCI address / UUID of every rank's device)
   dumped_outputs  (--dump-outputs DIR) the arrays written to DIR: what the last timed step completed, for comparing two builds
 """
 import argparse
@@ -75,14 +80,18 @@ def parse():
                          "flipped cloud, transpose back: pointnet2_modules.py:30-45) instead of epnet_sample_centres (FPS + row gather "
                          "of the centres, same idx / new_xyz): 6 instead of 3 launches per level on the sampling chain")
     ap.add_argument("--with-fp", action="store_true", help="also run the 4 three_nn + 4 three_interpolate FP ops")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the timed steps against the CPU oracle and measure everything else the line can carry: CPU "
+                         "baselines, per-kernel roofline, per-step spread, device copy, the extras (the four options below shape "
+                         "these; a plain run does none of it)")
     ap.add_argument("--cpu-scenes", type=int, default=None,
-                    help="scenes in the cpu_baseline sample (0 = skip; default 16 for config 2, 2 for config 5)")
-    ap.add_argument("--sweep", default="", help="comma list of extra batch sizes to time (reported under 'sweep')")
+                    help="(--full) scenes in the cpu_baseline sample (0 = skip; default 16 for config 2, 2 for config 5)")
+    ap.add_argument("--sweep", default="", help="(--full) comma list of extra batch sizes to time (reported under 'sweep')")
     ap.add_argument("--extras", default="b1,with_fp,kinds,config5",
-                    help="further measurements reported as sub-objects of the default N = 1 line (comma list of b1, with_fp, kinds, config5; "
-                         "empty = none)")
+                    help="(--full) further measurements reported as sub-objects of the N = 1 line (comma list of b1, with_fp, kinds, "
+                         "config5; empty = none)")
     ap.add_argument("--verify-scenes", type=int, default=1,
-                    help="scenes of the timed buffers rank 0 checks against the CPU oracle after the timed loop (0 = skip; "
+                    help="(--full) scenes of the timed buffers rank 0 checks against the CPU oracle after the timed loop (0 = skip; "
                          "the line then carries verified: null)")
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow EPNET_BENCH_DEVICE / EPNET_BENCH_BACKEND (all ranks on one device, gloo instead of RCCL): the line "
@@ -105,6 +114,8 @@ def parse():
         args.cpu_scenes = int(os.environ.get("EPNET_BENCH_CPU_SCENES", "16" if args.config == 2 else "2"))
     if args.with_fp and args.config != 2:
         ap.error("--with-fp belongs to config 2 (the FP modules of the RPN pyramid)")
+    if args.sweep and not args.full:
+        ap.error("--sweep times further runs: it belongs to --full")
     return args
 
 
@@ -489,6 +500,77 @@ def launch_check(args):
         dist.destroy_process_group()
 
 
+def kernel_figures(torch, ext, stack, xyz, args):
+    """per-kernel durations for --full: the same K steps replayed eagerly with HIP events around every launch; returns the
+    line's kernels, roofline and roofline_hbm_bound"""
+    stack.overlap = False  # single stream, unpipelined here, so that an event pair brackets exactly its own kernel
+    with OpTimer(torch, ext) as timer:
+        for _ in range(args.steps):
+            stack.run(xyz)
+        torch.cuda.synchronize()
+    fam = {}
+    for name, head, e0, e1 in timer.records:
+        label, nbytes = op_family(name, head)
+        f = fam.setdefault(label, {"ms": 0.0, "bytes": 0, "launches": 0, "shapes": {}})
+        ms = e0.elapsed_time(e1)
+        f["ms"] += ms
+        f["bytes"] += nbytes
+        f["launches"] += 1
+        if label in ("three_nn", "three_interpolate", "group"):   # several shapes under one label: keep them apart as well
+            shape = " ".join(str(v) for v in head[:5] if isinstance(v, (int, float, list, tuple)))
+            g = f["shapes"].setdefault(shape, {"ms": 0.0, "bytes": 0, "launches": 0})
+            g["ms"] += ms
+            g["bytes"] += nbytes
+            g["launches"] += 1
+    kernels = {}
+    for label, f in fam.items():
+        avg_ms = f["ms"] / f["launches"]
+        gbs = (f["bytes"] / f["launches"]) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        kernels[label] = {"launches_per_step": f["launches"] // args.steps, "avg_ms": round(avg_ms, 5),
+                          "step_ms": round(f["ms"] / args.steps, 5),
+                          "bytes_per_launch": f["bytes"] // f["launches"], "GBps": round(gbs, 2)}
+        if f["shapes"]:
+            kernels[label]["by_shape"] = {
+                shape: {"avg_ms": round(g["ms"] / g["launches"], 5),
+                        "GBps": round(g["bytes"] / g["launches"] / (g["ms"] / g["launches"] * 1e-3) / 1e9, 2) if g["ms"] > 0 else 0.0}
+                for shape, g in f["shapes"].items()}
+    def roof(label, note):
+        k = kernels[label]
+        traffic = pmc_traffic(label, args)
+        return {"bound": "hbm", "kernel": label, "kernel_symbols": FAMILY_KERNELS.get(label), "achieved": k["GBps"],
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(k["GBps"] / HBM_PEAK_GBS, 6), "traffic": traffic,
+                "traffic_source": (PMC_PROFILE + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, scaled by scenes per launch)")
+                if traffic else None, "avg_launch_ms": k["avg_ms"], "note": note}
+
+    longest, dominant = pick_dominant(kernels)
+    fps_note = ("FPS is a chain of M-1 dependent arg-max rounds per scene (latency bound, one workgroup per scene, ~0.6 us per "
+                "round): its HBM fraction is tiny by construction; see roofline_hbm_bound for the bandwidth-bound kernel")
+    grp_note = ("grouping = [grouped xyz - centre ; grouped features] of BOTH MSG scales of a level (epnet_group_concat_multi: one "
+                "call per level, 4 per step, the level-1 one without features; per call the centred-xyz kernel of each scale and "
+                "one row gather serving both scales): feature rows staged in LDS once, random reads from LDS, 16-byte coalesced "
+                "streaming writes; a plain device-to-device copy on this box runs at device_copy_GBps")
+    roofline = roof(dominant, fps_note if dominant.startswith("fps") else grp_note)
+    roofline["dominant_by_time"] = {"kernel": longest, "step_ms": kernels[longest]["step_ms"],
+                                    "chosen_step_ms": kernels[dominant]["step_ms"]}
+    hbm_label = max((k for k in kernels if not k.startswith("fps")), key=lambda k: kernels[k]["step_ms"])
+    roofline_hbm = roof(hbm_label, grp_note if hbm_label.startswith("group") else "")
+    return kernels, roofline, roofline_hbm
+
+
+def device_copy_gbps(torch, dev):
+    """achievable secondary denominator: a plain device-to-device copy of 2 GiB on `dev`, GB/s"""
+    src = torch.empty((1 << 29,), dtype=torch.float32, device=dev)
+    dst = torch.empty_like(src)
+    dst.copy_(src)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        dst.copy_(src)
+    e1.record()
+    torch.cuda.synchronize()
+    return 5 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9   # bytes read + bytes written
+
+
 def main():
     args = parse()
     # --gpus N without a torch.distributed.run environment: start the N ranks as child processes BEFORE this process
@@ -507,9 +589,9 @@ def main():
     import torch.distributed as dist
 
     rank, local_rank, world = scene_shard.env_world()
-    # CPU baselines first: the multi-core one forks workers, which must happen before this process touches the GPU
+    # CPU baselines (--full) first: the multi-core one forks workers, which must happen before this process touches the GPU
     cpu = cpu_multi = None
-    if rank == 0 and world == 1 and args.cpu_scenes > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_scenes > 0:
         cpu_multi = cpu_baseline_multicore(args.kind, args.points, max(1, min(16, os.cpu_count() or 1)), args.cfg,
                                            per_proc=2 if args.config == 2 else 1)
         cpu = cpu_baseline(args.kind, args.points, args.cpu_scenes, args.cfg)
@@ -633,12 +715,13 @@ def main():
     my_ms = elapsed_own / args.steps * 1e3
     per_rank = scene_shard.gather_over_ranks({"ms_per_step": round(my_ms, 4), "device": scene_shard.device_identity(dev)})
     devices_distinct = scene_shard.distinct_devices([r_["device"] for r_ in per_rank])
-    spread = dispersion(step, args.steps)
-    identity_share = stack.chain_identity_share()
+    # ---- everything below up to the line is --full: a plain run reports the timed steps alone
+    spread = dispersion(step, args.steps) if args.full else {}
+    identity_share = stack.chain_identity_share() if args.full else None
 
     # ---- what the timed steps left in the buffers, against the oracle (rank 0, outside every timed region)
     verification = None
-    if rank == 0 and args.verify_scenes > 0:
+    if args.full and rank == 0 and args.verify_scenes > 0:
         picks = sorted({0, args.batch - 1} if args.verify_scenes > 1 else {0})
         picks += [s_ for s_ in range(1, args.batch - 1)][:max(0, args.verify_scenes - len(picks))]
         mism = verify_stack(stack, batches, step, picks)
@@ -650,58 +733,9 @@ def main():
                                       "pipelined HIP-graph replays" if (args.pipelined and not args.no_graph) else
                                       ("HIP-graph replays" if not args.no_graph else "eager steps"))}
 
-    # ---- per-kernel durations: the same K steps replayed eagerly with HIP events around every launch
-    stack.overlap = False  # single stream, unpipelined here, so that an event pair brackets exactly its own kernel
-    with OpTimer(torch, ext) as timer:
-        for _ in range(args.steps):
-            stack.run(xyz)
-        torch.cuda.synchronize()
-    fam = {}
-    for name, head, e0, e1 in timer.records:
-        label, nbytes = op_family(name, head)
-        f = fam.setdefault(label, {"ms": 0.0, "bytes": 0, "launches": 0, "shapes": {}})
-        ms = e0.elapsed_time(e1)
-        f["ms"] += ms
-        f["bytes"] += nbytes
-        f["launches"] += 1
-        if label in ("three_nn", "three_interpolate", "group"):   # several shapes under one label: keep them apart as well
-            shape = " ".join(str(v) for v in head[:5] if isinstance(v, (int, float, list, tuple)))
-            g = f["shapes"].setdefault(shape, {"ms": 0.0, "bytes": 0, "launches": 0})
-            g["ms"] += ms
-            g["bytes"] += nbytes
-            g["launches"] += 1
-    kernels = {}
-    for label, f in fam.items():
-        avg_ms = f["ms"] / f["launches"]
-        gbs = (f["bytes"] / f["launches"]) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        kernels[label] = {"launches_per_step": f["launches"] // args.steps, "avg_ms": round(avg_ms, 5),
-                          "step_ms": round(f["ms"] / args.steps, 5),
-                          "bytes_per_launch": f["bytes"] // f["launches"], "GBps": round(gbs, 2)}
-        if f["shapes"]:
-            kernels[label]["by_shape"] = {
-                shape: {"avg_ms": round(g["ms"] / g["launches"], 5),
-                        "GBps": round(g["bytes"] / g["launches"] / (g["ms"] / g["launches"] * 1e-3) / 1e9, 2) if g["ms"] > 0 else 0.0}
-                for shape, g in f["shapes"].items()}
-    def roof(label, note):
-        k = kernels[label]
-        traffic = pmc_traffic(label, args)
-        return {"bound": "hbm", "kernel": label, "kernel_symbols": FAMILY_KERNELS.get(label), "achieved": k["GBps"],
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(k["GBps"] / HBM_PEAK_GBS, 6), "traffic": traffic,
-                "traffic_source": (PMC_PROFILE + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, scaled by scenes per launch)")
-                if traffic else None, "avg_launch_ms": k["avg_ms"], "note": note}
-
-    longest, dominant = pick_dominant(kernels)
-    fps_note = ("FPS is a chain of M-1 dependent arg-max rounds per scene (latency bound, one workgroup per scene, ~0.6 us per "
-                "round): its HBM fraction is tiny by construction; see roofline_hbm_bound for the bandwidth-bound kernel")
-    grp_note = ("grouping = [grouped xyz - centre ; grouped features] of BOTH MSG scales of a level (epnet_group_concat_multi: one "
-                "call per level, 4 per step, the level-1 one without features; per call the centred-xyz kernel of each scale and "
-                "one row gather serving both scales): feature rows staged in LDS once, random reads from LDS, 16-byte coalesced "
-                "streaming writes; a plain device-to-device copy on this box runs at device_copy_GBps")
-    roofline = roof(dominant, fps_note if dominant.startswith("fps") else grp_note)
-    roofline["dominant_by_time"] = {"kernel": longest, "step_ms": kernels[longest]["step_ms"],
-                                    "chosen_step_ms": kernels[dominant]["step_ms"]}
-    hbm_label = max((k for k in kernels if not k.startswith("fps")), key=lambda k: kernels[k]["step_ms"])
-    roofline_hbm = roof(hbm_label, grp_note if hbm_label.startswith("group") else "")
+    kernels = roofline = roofline_hbm = None
+    if args.full:
+        kernels, roofline, roofline_hbm = kernel_figures(torch, ext, stack, xyz, args)
     stack_bytes = (sa_stack.sa_algorithmic_bytes(args.points, args.cfg["npoints"], args.cfg["nsamples"], args.cfg["feat_channels"])["total"]
                    + (sa_stack.fp_algorithmic_bytes()["total"] if args.with_fp else 0))
     stack_gbs = (value / args.points) * stack_bytes / 1e9 / world
@@ -714,7 +748,7 @@ def main():
     # ---- further lines of the same run (N = 1, default configuration only), each verified against the oracle like the
     # headline: the single-scene latency, the step with the FP ops, and BASELINE config 5
     extras = {}
-    if world == 1 and args.config == 2 and not args.with_fp and args.extras:
+    if args.full and world == 1 and args.config == 2 and not args.with_fp and args.extras:
         del stack, xyz, batches, step
         torch.cuda.empty_cache()
 
@@ -753,20 +787,9 @@ def main():
         if "config5" in names:
             extra("config5", 256, max(3, args.steps // 4), cfg=sa_stack.CONFIGS[5],
                   note="BASELINE config 5: dense 65536-point kitti-like scenes, one level -- scene index, FPS 16384, ball query "
-                       "r 0.5 / nsample 64, grouping of coordinates and 64 feature channels (python bench.py --config 5 for the full line)")
+                       "r 0.5 / nsample 64, grouping of coordinates and 64 feature channels (python bench.py --config 5 --full for the full line)")
 
-    # achievable secondary denominator: a plain device-to-device copy of 2 GiB on this box
-    src = torch.empty((1 << 29,), dtype=torch.float32, device=dev)
-    dst = torch.empty_like(src)
-    dst.copy_(src)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
-        dst.copy_(src)
-    e1.record()
-    torch.cuda.synchronize()
-    copy_gbs = 5 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9   # bytes read + bytes written
-    del src, dst
+    copy_gbs = device_copy_gbps(torch, dev) if args.full else None
 
     if rank == 0:
         levels = len(args.cfg["npoints"])
@@ -784,7 +807,7 @@ def main():
                        "SA-level points/sec per GPU (dense 65536-pt scene, BASELINE config 5) + % HBM roofline"),
             "value": round(value, 1), "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "%d x %d-pt %s scenes per GPU per step through %s, %s launch"
                                    % (args.batch, args.points, args.kind, shape, "eager" if args.no_graph else "HIP-graph"),
                        "baseline_config": args.config, "levels": levels,
@@ -792,22 +815,25 @@ def main():
                        "ball_queries_in_stage_s_levels": [v + 1 for v in sorted(stack_s_levels)], "points_per_scene": args.points, "parallelism": "scene-parallel x%d" % world},
             "points_per_s_per_gpu": round(value / world, 1),
             "stack_algorithmic_GBps_per_gpu": round(stack_gbs, 2), "stack_hbm_frac": round(stack_gbs / HBM_PEAK_GBS, 6),
-            "device_copy_GBps": round(copy_gbs, 1), "stack_frac_of_device_copy": round(stack_gbs / copy_gbs, 6),
-            "roofline": roofline, "roofline_hbm_bound": roofline_hbm, "kernels": kernels, "cpu_baseline": cpu,
-            "cpu_baseline_multicore": cpu_multi,
-            "verified": None if verification is None else verification["verified"], "verification": verification,
             "ranks_seen": ranks_seen, "devices_distinct": devices_distinct, "rehearsal": bool(args.rehearsal),
             "per_rank_ms_per_step": {"min": min(r_["ms_per_step"] for r_ in per_rank), "max": max(r_["ms_per_step"] for r_ in per_rank),
                                      "ranks": [r_["ms_per_step"] for r_ in per_rank]},
             "devices": [r_["device"] for r_ in per_rank],
-            "sampling_chain": {"enabled": bool(stack_chain), "identity_share_levels_2_up": identity_share,
-                               "note": "levels 2.. sample the centres of the level above: a scene whose tie-free prefix covers the "
-                                       "level's sample count takes idx = 0..m-1 without running rounds (epnet_sample_centres_chain)"},
         }
+        if args.full:
+            line.update({
+                "device_copy_GBps": round(copy_gbs, 1), "stack_frac_of_device_copy": round(stack_gbs / copy_gbs, 6),
+                "roofline": roofline, "roofline_hbm_bound": roofline_hbm, "kernels": kernels, "cpu_baseline": cpu,
+                "cpu_baseline_multicore": cpu_multi,
+                "verified": None if verification is None else verification["verified"], "verification": verification,
+                "sampling_chain": {"enabled": bool(stack_chain), "identity_share_levels_2_up": identity_share,
+                                   "note": "levels 2.. sample the centres of the level above: a scene whose tie-free prefix covers the "
+                                           "level's sample count takes idx = 0..m-1 without running rounds (epnet_sample_centres_chain)"},
+            })
         line.update(spread)
         if dumped is not None:
             line["dumped_outputs"] = dumped
-        if world > 1:
+        if args.full and world > 1:
             line["cpu_baseline_note"] = "the CPU baseline is timed in the N = 1 run only (rank 0 there has the host to itself)"
         if sweep:
             line["sweep"] = sweep
