@@ -4,6 +4,7 @@ The library is built in-tree by ``__graft_entry__.build()`` / ``make -C epnet_am
 lazy and LOUD: if the shared object is missing or lacks a symbol the header declares, a
 RuntimeError is raised -- there is no fallback path.
 """
+import contextlib
 import ctypes
 import os
 
@@ -22,6 +23,8 @@ SIGNATURES = {
     "epnet_abi_version": (_i, []),
     "epnet_strerror": (ctypes.c_char_p, [_i]),
     "epnet_last_hip_error": (ctypes.c_char_p, []),
+    "epnet_set_tuning": (_i, [ctypes.c_char_p, _i]),
+    "epnet_get_tuning": (_i, [ctypes.c_char_p, ctypes.POINTER(_i)]),
     "epnet_furthest_point_sampling": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "epnet_gather_points": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "epnet_gather_points_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -112,3 +115,22 @@ def check(code, what):
         msg = l.epnet_strerror(code).decode()
         hip = l.epnet_last_hip_error().decode()
         raise EpnetError("%s failed: %s%s" % (what, msg, (" [" + hip + "]") if (code == -2 and hip) else ""))
+
+
+@contextlib.contextmanager
+def tuning(**overrides):
+    """kernel-selection overrides for the body, by the names of the EPNET_* variables (-1 = the library's own choice), e.g.
+    ``with tuning(EPNET_BQ_PAIR=1): ...``; the previous values come back on exit, also when the body raises. An unknown name
+    or a value out of range raises, so that a typo cannot quietly test the default kernel."""
+    l = lib()
+    saved = []
+    try:
+        for name, value in overrides.items():
+            old = _i()
+            check(l.epnet_get_tuning(name.encode(), ctypes.byref(old)), "epnet_get_tuning(%s)" % name)
+            check(l.epnet_set_tuning(name.encode(), int(value)), "epnet_set_tuning(%s, %r)" % (name, value))
+            saved.append((name, old.value))
+        yield
+    finally:
+        for name, old in reversed(saved):
+            l.epnet_set_tuning(name.encode(), old)

@@ -10,7 +10,6 @@
 // scanning as soon as all its centres are full; the block leaves when all its waves have.
 //
 // d2 = (cx-x)*(cx-x) + (cy-y)*(cy-y) + (cz-z)*(cz-z) in source order, no contraction; strict '<'.
-#include <stdlib.h>
 
 #include "common.h"
 #include "dpp.h"
@@ -599,7 +598,7 @@ __global__ __launch_bounds__(kQThreads) void bq_query_kernel(int np, int m, BqSc
 // of that cut (nothing at or above it can be among the first nsample in index order): ONE walk however crowded the ball, and
 // 4 KB of LDS per wave instead of the N-bit bitmap's 8 KB at 65536 points, which held the kernel at half the waves a CU can
 // keep (the walk is a chain of dependent loads: 0.54 -> 0.32 ms at 32 scenes of BASELINE config 5). The lists are looked at once
-// per step of the walk (<= 2 rows = 128 appends per list).
+// per step of the walk (<= kRowsPerStep rows = kStepAppends appends per list).
 template <int DPL, int K, bool kStream>
 __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqScales<K> sc,
                                                               const float *__restrict__ new_xyz,
@@ -607,7 +606,11 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
                                                               const float *__restrict__ boxes,
                                                               const float *__restrict__ qboxes,
                                                               const float4 *__restrict__ order, int npc) {
-    constexpr int CAP = kStream ? (K == 1 ? 512 : 256) : 64, kStepAppends = 128;
+    constexpr int kRowsPerStep = 2;   // candidate rows of each centre per step of the walk (scan_pairs: p0, p2 | p1, p3)
+    constexpr int CAP = kStream ? (K == 1 ? 512 : 256) : 64, kStepAppends = kRowsPerStep * 64;
+    static_assert(CAP % 64 == 0, "the lists are selected and emitted in whole waves");
+    static_assert(!kStream || CAP - kStepAppends >= 64,
+                  "a cut list keeps nsample <= 64 entries (the launcher streams for nsample <= 64 only) and must take a step's appends");
     constexpr int kBitWords = kStream ? 0 : 64 * DPL;
     __shared__ unsigned s_pool[kQThreads / 64][kBitWords + 2 * K * CAP];   // (the bitmap of a crowded ball,) the hit lists
     __shared__ int s_quads[kQThreads / 64][2][64];
@@ -692,6 +695,7 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
     };
     // one candidate row of each centre per step (both loads in flight together); bucket_of(e, bit)
     auto scan_pairs = [&](unsigned long long cand0, unsigned long long cand1, auto &&bucket_of) {
+        static_assert(kRowsPerStep == 2, "the step below loads two rows of each centre");
         while (cand0 | cand1) {
             make_room();
             float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0, p3 = p0;
@@ -844,27 +848,22 @@ static int bq_query_launch(int b, int np, int m, const BqScales<K> &sc, const fl
     const float *boxes = (const float *)(sorted + (size_t)b * np);
     const float *qboxes = boxes + (size_t)b * (np / 64) * 6;
     // enough centres to fill the chip: two per wave (half the latency per centre); EPNET_BQ_PAIR=0/1 forces either
-    const char *pair_str = getenv("EPNET_BQ_PAIR");
-    const int pair_env = pair_str ? atoi(pair_str) : -1;
-    const bool pair = pair_env >= 0 ? pair_env != 0 : (long long)b * m >= 65536;
-    // EPNET_BQ_PAD_KB: LDS the launch reserves without using it -- fewer workgroups per CU, i.e. wave slots left for the short
-    // one-workgroup-per-scene kernels of the sampling chain that run beside a full-chip query (an experiment knob; default 0)
-    const char *pad_str = getenv("EPNET_BQ_PAD_KB");
-    const size_t pad = pad_str ? (size_t)atoi(pad_str) * 1024 : 0;
+    const int pair_force = tuning(kBqPair);
+    const bool pair = pair_force >= 0 ? pair_force != 0 : (long long)b * m >= 65536;
     if (pair) {
         dim3 grid(div_up(div_up(m, 2), kQThreads / 64), b);
         // streaming lists instead of the bitmap (see the kernel): where the bitmap costs occupancy, i.e. above 16384 points;
         // EPNET_BQ_STREAM=0/1 forces either (nsample <= 64 is a precondition of the streaming variant)
-        bool stream = np > 16384;
-        if (const char *e = getenv("EPNET_BQ_STREAM")) stream = atoi(e) != 0;
+        const int stream_force = tuning(kBqStream);
+        bool stream = stream_force >= 0 ? stream_force != 0 : np > 16384;
         for (int k = 0; k < K; ++k) stream = stream && sc.nsample[k] <= 64;
 #define EPNET_BQ2(D_)                                                                                                                   \
     do {                                                                                                                                \
         if (stream)                                                                                                                     \
-            hipLaunchKernelGGL((bq_query2_kernel<D_, K, true>), grid, dim3(kQThreads), pad, s, np, m, sc, new_xyz, sorted, boxes, qboxes, \
+            hipLaunchKernelGGL((bq_query2_kernel<D_, K, true>), grid, dim3(kQThreads), 0, s, np, m, sc, new_xyz, sorted, boxes, qboxes,   \
                                order, npc);                                                                                             \
         else                                                                                                                            \
-            hipLaunchKernelGGL((bq_query2_kernel<D_, K, false>), grid, dim3(kQThreads), pad, s, np, m, sc, new_xyz, sorted, boxes,       \
+            hipLaunchKernelGGL((bq_query2_kernel<D_, K, false>), grid, dim3(kQThreads), 0, s, np, m, sc, new_xyz, sorted, boxes,         \
                                qboxes, order, npc);                                                                                     \
     } while (0)
         switch (np / 2048) {
@@ -879,7 +878,7 @@ static int bq_query_launch(int b, int np, int m, const BqScales<K> &sc, const fl
         return check_launch("ball_query query");
     }
     dim3 grid(div_up(m, kQThreads / 64), b);
-#define EPNET_BQ(D_) hipLaunchKernelGGL((bq_query_kernel<D_, K>), grid, dim3(kQThreads), pad, s, np, m, sc, new_xyz, sorted, boxes, qboxes, order, npc)
+#define EPNET_BQ(D_) hipLaunchKernelGGL((bq_query_kernel<D_, K>), grid, dim3(kQThreads), 0, s, np, m, sc, new_xyz, sorted, boxes, qboxes, order, npc)
     switch (np / 2048) {
         case 1: EPNET_BQ(1); break;
         case 2: EPNET_BQ(2); break;
@@ -980,8 +979,8 @@ extern "C" int epnet_ball_query_ordered(int b, int n, int m, int nscales, const 
     for (int k = 0; ordered && k < nscales; ++k) ordered = nsamples[k] > 0 && idx[k] != nullptr;
     // what the order buys is cache hits on the point rows: nothing up to 16384 points (the scene's rows stay in L2 whatever the order:
     // 256 scenes, 16384 x 4096: 0.458 = 0.455 ms; 4096 x 1024: 0.108 -> 0.125), 31 % at 65536 (6.68 -> 4.58 ms). EPNET_BQ_ORDERED=0/1 forces.
-    const char *force = getenv("EPNET_BQ_ORDERED");
-    if (force ? atoi(force) == 0 : n <= 16384) ordered = false;
+    const int force = tuning(kBqOrdered);
+    if (force >= 0 ? force == 0 : n <= 16384) ordered = false;
     if (!ordered) return epnet_ball_query_indexed_multi(b, n, m, nscales, radii, nsamples, new_xyz, xyz, index, index_bytes, idx, stream);
     if (index_bytes < need || centre_index_bytes < need_c) return EPNET_ENOMEM;
     EPNET_REQUIRE(b <= 65535);

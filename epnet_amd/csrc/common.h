@@ -18,6 +18,12 @@ inline int check_launch(const char *where) {
     return EPNET_OK;
 }
 
+// The kernel-selection overrides (epnet_set_tuning, table in host.cpp): read once from the environment, then only through
+// tuning(). Each forces a kernel that the default dispatch picks for some other shape; none changes a result.
+enum Knob { kFpsPrune, kFpsPruneMin, kFpsPwaves, kFpsWaves, kBqPair, kBqStream, kBqOrdered, kNnTileMinBuckets, kKnobCount };
+// the override, else the knob's default; -1 = the launcher's own choice
+int tuning(Knob k);
+
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 inline long long div_up64(long long a, long long b) { return (a + b - 1) / b; }
 

@@ -27,7 +27,6 @@
 // Arithmetic: d = dx*dx + dy*dy + dz*dz evaluated left to right in fp32 without contraction
 // (-ffp-contract=off), then min with the running distance, as sampling_gpu.cu:133-135.
 #include <math.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -380,17 +379,14 @@ __device__ __forceinline__ void set_rank(VH &rk2, int j, unsigned r) {  // j is 
 // (distance bits << 32 | (0x3FFF - rank) << 10 | thread): the larger distance wins, equal distances go to the
 // smaller reference rank -- and after the round's single barrier the winner is read back with two
 // dependent LDS loads (key, then that thread's coordinates), no cross-lane reduction at all.
-// kCtr: also emit the selected points' coordinates (ctr, m x 3 floats): the gather that follows the sampling
-// in an SA module (pointnet2_modules.py:39-45) comes for free, the round's winner is in registers anyway.
-template <int kW, int PPT, bool kCtr, typename VF, typename VI, typename VH>
+template <int kW, int PPT, typename VF, typename VI, typename VH>
 __device__ __forceinline__ void fps_rounds(int m, const VF &x, const VF &y, const VF &z, VI &t, const VH &rk2,
                                            float cx, float cy, float cz, int *__restrict__ idxs,
-                                           float *__restrict__ ctr, int *__restrict__ tie_free = nullptr, int known = 0,
+                                           int *__restrict__ tie_free = nullptr, int known = 0,
                                            const float *__restrict__ xyz_in_order = nullptr, int detect_upto = 0x7fffffff) {
     __shared__ unsigned long long s_key[3];
     __shared__ float4 s_rec[2][64 * kW];  // one record slot per thread
     __shared__ int s_idx[kIdxBufP];
-    __shared__ float s_ctr[kCtr ? kIdxBufP * 3 : 1];
     const int q = threadIdx.x;
     const int lane = q & 63, wave = q >> 6;
     const int sub = lane & (PPT - 1);  // the slot this lane summarises (for its own part)
@@ -417,10 +413,9 @@ __device__ __forceinline__ void fps_rounds(int m, const VF &x, const VF &y, cons
     }
     if (q < 3) s_key[q] = 0ull;
     if (q == 0) s_idx[0] = 0;  // rank 0 == point 0
-    if (kCtr && q < 3) s_ctr[q] = q == 0 ? cx : (q == 1 ? cy : cz);
     // `known` leading samples are given (points 0 .. known-1 of the cloud in its own order: a sampling pyramid's chain,
     // epnet_sample_centres_chain): their rounds need no selection, only the distance updates -- no cross-wave exchange, no barrier
-    if (known > kIdxBufP || known > m || !xyz_in_order || kCtr) known = 0;
+    if (known > kIdxBufP || known > m || !xyz_in_order) known = 0;
     for (int i = q; i < known; i += 64 * kW) s_idx[i] = (int)rank14(i);
     __syncthreads();
     for (int it = 1; it < known; ++it) {
@@ -583,14 +578,9 @@ __device__ __forceinline__ void fps_rounds(int m, const VF &x, const VF &y, cons
         if (wave == 0) {
             s_idx[it & (kIdxBufP - 1)] = (int)(0x3FFFu - (klo >> 10));  // all lanes, same word; converted at the flush
             if (lane == 0) s_key[kb2] = 0ull;
-            if (kCtr && lane < 3) s_ctr[(it & (kIdxBufP - 1)) * 3 + lane] = lane == 0 ? cx : (lane == 1 ? cy : cz);
             if ((it & (kIdxBufP - 1)) == kIdxBufP - 1) {
                 const int base = it - (kIdxBufP - 1);
                 for (int e = lane; e < kIdxBufP; e += 64) idxs[base + e] = unrank14((unsigned)s_idx[e]);
-                if (kCtr) {
-#pragma unroll 1
-                    for (int e = lane; e < kIdxBufP * 3; e += 64) ctr[(size_t)base * 3 + e] = s_ctr[e];
-                }
             }
         }
         EPNET_STAMP(t5);
@@ -609,10 +599,6 @@ __device__ __forceinline__ void fps_rounds(int m, const VF &x, const VF &y, cons
     if (wave == 0) {
         const int base = (m - 1) & ~(kIdxBufP - 1);
         for (int e = lane; base + e < m; e += 64) idxs[base + e] = unrank14((unsigned)s_idx[e]);
-        if (kCtr) {
-#pragma unroll 1
-            for (int e = lane; e < (m - base) * 3; e += 64) ctr[(size_t)base * 3 + e] = s_ctr[e];
-        }
     }
 }
 
@@ -669,8 +655,8 @@ __global__ __launch_bounds__(64 * kW) void fps_pruned_kernel(int n, int m, const
             set_rank(rk2, j, 0xFFFFu);
         }
     }
-    fps_rounds<kW, PPT, false>(m, x, y, z, t, rk2, xyz[0], xyz[1], xyz[2], idxs, nullptr,
-                               prefix_out ? prefix_out + blockIdx.x : nullptr, 0, nullptr, prefix_cap);
+    fps_rounds<kW, PPT>(m, x, y, z, t, rk2, xyz[0], xyz[1], xyz[2], idxs, prefix_out ? prefix_out + blockIdx.x : nullptr, 0,
+                        nullptr, prefix_cap);
     if (temp) {
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
@@ -682,10 +668,10 @@ __global__ __launch_bounds__(64 * kW) void fps_pruned_kernel(int n, int m, const
 
 // Same rounds over a scene index built beforehand (spatial.h: cell-sorted float4 copy x, y, z, original index;
 // padding entries carry index -1). Needs no dynamic LDS, so it shares a CU with the bandwidth-bound kernels.
-template <int kW, int PPT, bool kCtr>
+template <int kW, int PPT>
 __global__ __launch_bounds__(64 * kW) void fps_indexed_kernel(int n, int m, const float4 *__restrict__ sorted,
                                                               float *__restrict__ temp, int *__restrict__ idxs,
-                                                              float *__restrict__ ctr, const int *__restrict__ prefix_in,
+                                                              const int *__restrict__ prefix_in,
                                                               int *__restrict__ prefix_out, const float *__restrict__ xyz,
                                                               int prefix_cap, int prologue_init) {
     typedef float vecf __attribute__((ext_vector_type(PPT)));
@@ -700,7 +686,6 @@ __global__ __launch_bounds__(64 * kW) void fps_indexed_kernel(int n, int m, cons
     sorted += (size_t)blockIdx.x * NP;
     if (temp) temp += (size_t)blockIdx.x * n;
     idxs += (size_t)blockIdx.x * m;
-    if (kCtr) ctr += (size_t)blockIdx.x * m * 3;
     typedef int vech __attribute__((ext_vector_type(PPT / 2)));
     vecf x, y, z;
     veci t;
@@ -727,9 +712,8 @@ __global__ __launch_bounds__(64 * kW) void fps_indexed_kernel(int n, int m, cons
         }
     }
     __syncthreads();
-    fps_rounds<kW, PPT, kCtr>(m, x, y, z, t, rk2, s_first[0], s_first[1], s_first[2], idxs, ctr,
-                              prefix_out ? prefix_out + blockIdx.x : nullptr, known,
-                              xyz ? xyz + (size_t)blockIdx.x * n * 3 : nullptr, prefix_cap);
+    fps_rounds<kW, PPT>(m, x, y, z, t, rk2, s_first[0], s_first[1], s_first[2], idxs, prefix_out ? prefix_out + blockIdx.x : nullptr,
+                        known, xyz ? xyz + (size_t)blockIdx.x * n * 3 : nullptr, prefix_cap);
     if (temp) {
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
@@ -754,7 +738,7 @@ __device__ __forceinline__ int unrank16(unsigned r) { return (int)(bitrev_lg(r >
 // 16 waves 0.88 / 1.18 us per round, 8 waves 1.11 / 1.47, 4 waves 1.50 / 1.97 -- the round is a chain of latencies through ONE
 // wave (winner read-back -> box tests -> row load -> update + bucket maximum -> the wave's arg-max -> LDS atomic -> barrier), and
 // a wave with four buckets per lane runs four box tests and up to four times the row updates back to back; the instructions
-// the sixteen waves issue in total are not what bounds it. 16 is the default (EPNET_FPS_BIG_WAVES = 4 | 8 keeps the others).
+// the sixteen waves issue in total are not what bounds it: 16 it is.
 template <int kW>
 __global__ __launch_bounds__(64 * kW) void fps_bigscene_kernel(int n, int np, int m, const float *__restrict__ xyz,
                                                                const float4 *__restrict__ sorted,
@@ -1061,6 +1045,12 @@ using namespace epnet;
 // THIS sampling whose maximum was unique (initialised by fps_prefix_kernel) where the kernel can tell. Both may be NULL.
 __global__ void fps_prefix_kernel(int m, const int *__restrict__ skip, int *__restrict__ idx, int *__restrict__ prefix_out, int init);
 
+// does the spatially-pruned kernel take a plain sampling of m from n points? 1024 < n <= 16384 (EPNET_FPS_PRUNE=0 forces the
+// brute-force path, EPNET_FPS_PRUNE_MIN raises the lower end)
+static bool fps_prune_applies(int n, int m) {
+    return tuning(kFpsPrune) != 0 && n > 1024 && n > tuning(kFpsPruneMin) && n <= 16384 && m > 1;
+}
+
 // prologue_init >= 0: skip / prefix_out still want their fps_prefix_kernel treatment with that initial value -- folded into the
 // register-resident kernel, launched separately in front of the others
 static int fps_plain(int b, int n, int m, const float *xyz, float *temp, int *idx, const int *skip, int *prefix_out,
@@ -1074,23 +1064,17 @@ static int fps_plain(int b, int n, int m, const float *xyz, float *temp, int *id
     const int bs_ref = 1 << lg;
     dim3 grid(b);
     const int J = div_up(n, bs_ref);
-    // 1024 < n <= 16384: exact spatially-pruned kernel (EPNET_FPS_PRUNE=0 forces the brute-force path)
-    // (the tuning variables are read on every call, so that the one-process GPU test run reaches every variant)
-    const bool prune_enabled = !(getenv("EPNET_FPS_PRUNE") && atoi(getenv("EPNET_FPS_PRUNE")) == 0);
-    const int prune_min = getenv("EPNET_FPS_PRUNE_MIN") ? atoi(getenv("EPNET_FPS_PRUNE_MIN")) : 1024;
     auto prefix_first = [&]() -> int {   // the kernels below do not do the prologue themselves
         if (prologue_init < 0) return EPNET_OK;
         hipLaunchKernelGGL(fps_prefix_kernel, dim3(b), dim3(256), 0, s, m, skip, idx, prefix_out, prologue_init);
         return check_launch("sampling prefix");
     };
-    if (prune_enabled && n > 1024 && n > prune_min && n <= 16384 && m > 1) {
+    if (fps_prune_applies(n, m)) {  // exact spatially-pruned kernel
         if (int rc = prefix_first()) return rc;
         // 64-point slots: 4 waves x {8,16,32} slots, 8 waves above 8192 points (EPNET_FPS_PWAVES overrides)
         int waves = n > 8192 ? 8 : 4;
-        if (const char *e = getenv("EPNET_FPS_PWAVES")) {
-            const int w = atoi(e);
-            if ((w == 2 || w == 4 || w == 8) && div_up(n, 64 * w) <= 32 && div_up(n, 64 * w) >= 1) waves = w;
-        }
+        const int w = tuning(kFpsPwaves);
+        if (w > 0 && div_up(n, 64 * w) <= 32) waves = w;
         const int ppt_need = div_up(n, 64 * waves);
         const int ppt = ppt_need <= 8 ? 8 : ppt_need <= 16 ? 16 : 32;
         const size_t lds = (size_t)(kCells + kCells / (kCells / (64 * waves)) + 64) * sizeof(int) + (size_t)64 * waves * ppt * 2;
@@ -1100,10 +1084,6 @@ static int fps_plain(int b, int n, int m, const float *xyz, float *temp, int *id
             if (ppt == 8) EPNET_FPS_PRUNED(8, 8);
             else if (ppt == 16) EPNET_FPS_PRUNED(8, 16);
             else EPNET_FPS_PRUNED(8, 32);
-        } else if (waves == 2) {
-            if (ppt == 8) EPNET_FPS_PRUNED(2, 8);
-            else if (ppt == 16) EPNET_FPS_PRUNED(2, 16);
-            else EPNET_FPS_PRUNED(2, 32);
         } else {
             if (ppt == 8) EPNET_FPS_PRUNED(4, 8);
             else if (ppt == 16) EPNET_FPS_PRUNED(4, 16);
@@ -1124,10 +1104,8 @@ static int fps_plain(int b, int n, int m, const float *xyz, float *temp, int *id
         // few scenes of 512 < n <= 1024 points: the chip is idle anyway and a round is shorter with 2 slots per
         // thread on 8 waves (0.48 us) than with 16 slots on one wave (0.66 us); many small scenes pack best at 1 wave
         if (n > 512 && b <= 512 && bs_ref / 64 >= 8 && waves < 8) waves = 8;
-        if (const char *e = getenv("EPNET_FPS_WAVES")) {
-            const int w = atoi(e);
-            if (w >= 1 && w <= bs_ref / 64 && (w & (w - 1)) == 0 && (bs_ref / (64 * w)) * J <= 16) waves = w;
-        }
+        const int w = tuning(kFpsWaves);  // (a power of two, or -1)
+        if (w >= 1 && w <= bs_ref / 64 && (bs_ref / (64 * w)) * J <= 16) waves = w;
         const int ppt = (bs_ref / (64 * waves)) * J;
 #define EPNET_FPS_LAUNCH(W_, P_) \
     hipLaunchKernelGGL((fps_wave_kernel<W_, P_>), grid, dim3(64 * W_), 0, s, n, m, lg, xyz, temp, idx, skip, prefix_out, prologue_init)
@@ -1166,11 +1144,8 @@ extern "C" int epnet_furthest_point_sampling(int b, int n, int m, const float *x
 
 // does the kernel the dispatch above / below picks report its tie-free rounds? (the pruned kernels do)
 static bool fps_detects_ties(int n, int m, bool indexed) {
-    if (m <= 1 || n <= 1024 || n > 16384) return false;
-    if (indexed) return true;
-    const bool prune_enabled = !(getenv("EPNET_FPS_PRUNE") && atoi(getenv("EPNET_FPS_PRUNE")) == 0);
-    const int prune_min = getenv("EPNET_FPS_PRUNE_MIN") ? atoi(getenv("EPNET_FPS_PRUNE_MIN")) : 1024;
-    return prune_enabled && n > prune_min;
+    if (indexed) return m > 1 && n > 1024 && n <= 16384;
+    return fps_prune_applies(n, m);
 }
 
 // scenes whose first m points are known to be the samples (skip[b] >= m): idx = 0 .. m-1, and the knowledge is passed on;
@@ -1226,7 +1201,6 @@ static int fps_over_index(int b, int n, int m, const float *xyz, void *index, si
                           float *new_xyz, hipStream_t s, const int *skip = nullptr, int *prefix_out = nullptr,
                           int prefix_cap = 0x7fffffff) {
     const size_t need = scene_index_bytes(b, n);
-    bool centres_done = false;
     int rc;
     const bool plain = need == 0 || !index || n <= 1024 || m <= 1 || (n > 16384 && !temp);
     int fold_init = -1;   // >= 0: the known prefixes / the tie-free counts still need their initial treatment (fps_prologue)
@@ -1257,43 +1231,24 @@ static int fps_over_index(int b, int n, int m, const float *xyz, void *index, si
             const int np = scene_index_np(n);
             const float *bucket_boxes = (const float *)(sorted + (size_t)b * np);
             float *tsort = scene_index_sampling_scratch(b, n, index);
-            const int big_waves = getenv("EPNET_FPS_BIG_WAVES") ? atoi(getenv("EPNET_FPS_BIG_WAVES")) : 16;
-            if (big_waves == 4)
-                hipLaunchKernelGGL(pruned::fps_bigscene_kernel<4>, grid, dim3(256), 0, s, n, np, m, xyz, sorted, bucket_boxes, temp, tsort, idx, skip);
-            else if (big_waves == 8)
-                hipLaunchKernelGGL(pruned::fps_bigscene_kernel<8>, grid, dim3(512), 0, s, n, np, m, xyz, sorted, bucket_boxes, temp, tsort, idx, skip);
-            else
-                hipLaunchKernelGGL(pruned::fps_bigscene_kernel<16>, grid, dim3(1024), 0, s, n, np, m, xyz, sorted, bucket_boxes, temp, tsort, idx, skip);
+            hipLaunchKernelGGL(pruned::fps_bigscene_kernel<16>, grid, dim3(1024), 0, s, n, np, m, xyz, sorted, bucket_boxes, temp, tsort, idx, skip);
         } else {
-            const int wide = getenv("EPNET_FPS_WIDE") ? atoi(getenv("EPNET_FPS_WIDE")) : 0;
-            // the centres can come out of the sampling kernel itself (kCtr: the round's winner is in registers anyway) or from a
-            // small gather afterwards. In-kernel costs wave 0 an LDS write per round and 12 KB more LDS: 1.7 % on one scene,
-            // 5 % in the software-pipelined stack -- more than the extra launch, so the separate gather is the default
-            const bool ctr_in_kernel = getenv("EPNET_FPS_CTR") && atoi(getenv("EPNET_FPS_CTR")) != 0 && !skip;
-#define EPNET_FPS_INDEXED(W_, P_)                                                                                          \
-    do {                                                                                                                   \
-        if (new_xyz && ctr_in_kernel)                                                                                      \
-            hipLaunchKernelGGL((pruned::fps_indexed_kernel<W_, P_, true>), grid, dim3(64 * W_), 0, s, n, m, sorted, temp, \
-                               idx, new_xyz, skip, prefix_out, xyz, prefix_cap, fold_init);                                \
-        else                                                                                                               \
-            hipLaunchKernelGGL((pruned::fps_indexed_kernel<W_, P_, false>), grid, dim3(64 * W_), 0, s, n, m, sorted, temp, \
-                               idx, (float *)nullptr, skip, prefix_out, xyz, prefix_cap, fold_init);                       \
-    } while (0)
+            // (the centres come from the small gather below: written by the sampling kernel itself they cost wave 0 an LDS write
+            // per round and 12 KB more LDS, 1.7 % on one scene and 5 % in the software-pipelined stack -- more than the launch)
+#define EPNET_FPS_INDEXED(W_, P_)                                                                                                     \
+    hipLaunchKernelGGL((pruned::fps_indexed_kernel<W_, P_>), grid, dim3(64 * W_), 0, s, n, m, sorted, temp, idx, skip, prefix_out, xyz, \
+                       prefix_cap, fold_init)
             switch (scene_index_np(n)) {
                 case 2048: EPNET_FPS_INDEXED(4, 8); break;
                 case 4096: EPNET_FPS_INDEXED(4, 16); break;
                 case 8192: EPNET_FPS_INDEXED(4, 32); break;
-                default:
-                    if (wide) EPNET_FPS_INDEXED(16, 16);
-                    else EPNET_FPS_INDEXED(8, 32);
-                    break;
+                default: EPNET_FPS_INDEXED(8, 32); break;
             }
 #undef EPNET_FPS_INDEXED
-            centres_done = new_xyz != nullptr && ctr_in_kernel;
         }
         rc = check_launch("furthest_point_sampling");
     }
-    if (rc || !new_xyz || centres_done) return rc;
+    if (rc || !new_xyz) return rc;
     if (m == 0) return EPNET_OK;
     EPNET_REQUIRE(xyz && b <= 65535);
     launch_gather_centres(b, n, m, xyz, idx, new_xyz, s);

@@ -14,7 +14,6 @@
 //             to grad_points with plain coalesced stores: no global atomics, no cross-workgroup
 //             races. Summation order within a row is still unspecified (as it is in the
 //             reference), so gradients are compared to 1e-5, not bit-for-bit.
-#include <stdlib.h>
 
 #include "common.h"
 #include "spatial.h"
@@ -593,7 +592,7 @@ static int launch_gather_rows(int b, int c, int n, long long p, const float *poi
         int rows = kLdsBudget / (n * 4);
         if (rows > c) rows = c;
         if (rows > 32) rows = 32;
-        const bool quad = (c & 3) == 0 && (n & 3) == 0 && rows >= 4 && ((uintptr_t)points & 15) == 0 && !getenv("EPNET_GATHER_NO_QUAD");
+        const bool quad = (c & 3) == 0 && (n & 3) == 0 && rows >= 4 && ((uintptr_t)points & 15) == 0;
         if (quad) rows &= ~3;  // whole groups of four channel rows
         const int chunks = div_up(c, rows);
         // enough workgroups to fill the chip; every tile re-stages its rows, so keep tiles >= 2048 positions
@@ -770,7 +769,7 @@ extern "C" int epnet_group_concat_multi(int b, int c, int n, int npoints, int ns
         rows = kLdsBudget / (n * 4);
         if (rows > c) rows = c;
         if (rows > 32) rows = 32;
-        quad = (c & 3) == 0 && (n & 3) == 0 && rows >= 4 && ((uintptr_t)features & 15) == 0 && !getenv("EPNET_GATHER_NO_QUAD");
+        quad = (c & 3) == 0 && (n & 3) == 0 && rows >= 4 && ((uintptr_t)features & 15) == 0;
         if (quad) rows &= ~3;
         for (int k = 0; k < 2 && fused; ++k) {
             const long long p = (long long)npoints * nsamples[k];

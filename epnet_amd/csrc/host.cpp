@@ -1,9 +1,12 @@
 // host.cpp -- the non-kernel part of libepnet_hip.so: ABI bookkeeping, error strings and the two
 // roipool3d ops that are HOST-memory ops in the reference itself (roipool3d.cpp:97-195; they run
 // inside DataLoader worker processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157).
+#include <limits.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <string>
 
 #include "common.h"
@@ -15,6 +18,51 @@ static thread_local std::string g_last_hip_error;
 int record_hip_error(hipError_t e, const char *where) {
     g_last_hip_error = std::string(where) + ": " + hipGetErrorString(e);
     return EPNET_ELAUNCH;
+}
+
+// ---- kernel-selection overrides (epnet_set_tuning; the knobs are listed in epnet_ops.h)
+static const struct {
+    const char *name;
+    int lo, hi, dflt;  // accepted values besides -1; what tuning() reports without an override (-1: the launcher decides)
+} kKnobs[kKnobCount] = {  // in Knob order
+    {"EPNET_FPS_PRUNE", 0, 1, 1},     {"EPNET_FPS_PRUNE_MIN", 0, INT_MAX, 1024}, {"EPNET_FPS_PWAVES", 4, 8, -1},
+    {"EPNET_FPS_WAVES", 1, 16, -1},   {"EPNET_BQ_PAIR", 0, 1, -1},               {"EPNET_BQ_STREAM", 0, 1, -1},
+    {"EPNET_BQ_ORDERED", 0, 1, -1},   {"EPNET_NN_TILE_MIN_BUCKETS", 0, INT_MAX, 4096},
+};
+static std::atomic<int> g_knob[kKnobCount];  // -1: no override
+
+static bool knob_accepts(int k, long v) {  // (wave counts: powers of two)
+    const bool pow2 = k == kFpsPwaves || k == kFpsWaves;
+    return v == -1 || (v >= kKnobs[k].lo && v <= kKnobs[k].hi && (!pow2 || (v & (v - 1)) == 0));
+}
+
+static int find_knob(const char *name) {
+    for (int k = 0; name && k < kKnobCount; ++k)
+        if (strcmp(name, kKnobs[k].name) == 0) return k;
+    return -1;
+}
+
+// the only place the library reads its environment, once (an A/B run such as `EPNET_BQ_PAIR=1 python bench.py` needs no code
+// change); a malformed or out-of-range value is ignored
+static bool seed_from_env() {
+    for (int k = 0; k < kKnobCount; ++k) {
+        const char *e = getenv(kKnobs[k].name);
+        char *end = nullptr;
+        const long v = e ? strtol(e, &end, 10) : -1;
+        g_knob[k].store(e && end != e && *end == '\0' && knob_accepts(k, v) ? (int)v : -1, std::memory_order_relaxed);
+    }
+    return true;
+}
+
+static std::atomic<int> &knob(int k) {
+    static const bool seeded = seed_from_env();  // on first use; thread-safe (C++11)
+    (void)seeded;
+    return g_knob[k];
+}
+
+int tuning(Knob k) {
+    const int v = knob(k).load(std::memory_order_relaxed);
+    return v >= 0 ? v : kKnobs[k].dflt;
 }
 
 // pt_in_box3d_cpu, lib/utils/roipool3d/src/roipool3d.cpp:82-95. The box-only terms are hoisted
@@ -53,7 +101,7 @@ extern "C" int epnet_abi_version(void) { return EPNET_ABI_VERSION; }
 extern "C" const char *epnet_strerror(int code) {
     switch (code) {
         case EPNET_OK: return "ok";
-        case EPNET_EINVAL: return "invalid argument (negative size or NULL pointer)";
+        case EPNET_EINVAL: return "invalid argument (negative size, NULL pointer, unknown tuning name or value)";
         case EPNET_ELAUNCH: return "HIP kernel launch failed";
         case EPNET_ENOMEM: return "workspace too small";
         case EPNET_ELIMIT: return "problem size outside the supported range";
@@ -62,6 +110,20 @@ extern "C" const char *epnet_strerror(int code) {
 }
 
 extern "C" const char *epnet_last_hip_error(void) { return g_last_hip_error.c_str(); }
+
+extern "C" int epnet_set_tuning(const char *name, int value) {
+    const int k = find_knob(name);
+    EPNET_REQUIRE(k >= 0 && knob_accepts(k, value));
+    knob(k).store(value, std::memory_order_relaxed);
+    return EPNET_OK;
+}
+
+extern "C" int epnet_get_tuning(const char *name, int *value) {
+    const int k = find_knob(name);
+    EPNET_REQUIRE(k >= 0 && value);
+    *value = knob(k).load(std::memory_order_relaxed);
+    return EPNET_OK;
+}
 
 extern "C" int epnet_pts_in_boxes3d_host(int64_t *pts_flag, const float *pts, const float *boxes3d, int64_t boxes_num,
                                          int64_t pts_num) {

@@ -17,7 +17,6 @@
 // loops over a chunk of channels (the reference re-reads idx and weight for every channel).
 #include <limits.h>
 #include <math.h>
-#include <stdlib.h>
 
 #include "common.h"
 #include "dpp.h"
@@ -829,9 +828,8 @@ extern "C" int epnet_three_nn_indexed(int b, int n, int m, const float *unknown,
     const size_t need_u = scene_index_bytes(b, n);
     // the bucket-of-unknowns kernel does a long serial walk per wave: it wins once there are enough buckets to fill
     // the chip (measured: 4096 buckets 0.20 vs 0.26 ms, 1024 buckets 0.12 vs 0.06 ms)
-    const char *env_min = getenv("EPNET_NN_TILE_MIN_BUCKETS");  // tests force either kernel
-    const long long min_buckets = env_min ? atoll(env_min) : 4096;
-    if (need_u != 0 && unknown_index && (npk >> 6) <= kNnTileMaxBoxes && (long long)b * (scene_index_np(n) >> 6) >= min_buckets) {
+    // (EPNET_NN_TILE_MIN_BUCKETS moves the threshold: tests force either kernel)
+    if (need_u != 0 && unknown_index && (npk >> 6) <= kNnTileMaxBoxes && (long long)b * (scene_index_np(n) >> 6) >= tuning(kNnTileMinBuckets)) {
         if (unknown_index_bytes < need_u) return EPNET_ENOMEM;
         const int npu = scene_index_np(n);
         const float4 *sorted_u = (const float4 *)unknown_index;

@@ -20,8 +20,9 @@
 // nsample times, FPS-subset points near the sensor are nearest to hundreds of unknowns), no list is walked through a
 // chain of dependent loads, and nothing is atomic. The order of the terms inside a run is whatever the counting sort
 // produced (the reference's atomicAdd order is unspecified as well).
+// The tiling, the partition and the workspace size are functions of the problem shape alone: no tuning value enters them, so
+// a *_workspace_bytes query and the launch it sizes always agree.
 #pragma once
-#include <stdlib.h>
 
 #include "common.h"
 #include "spatial.h"
@@ -67,10 +68,6 @@ inline int tile_floats(int n, int div, long long row_floats) {
     long long t = ((long long)kLdsLimit / 4 - n_pad - 2 * kThreads);
     if (t > kMaxRowFloats) t = kMaxRowFloats;
     if (t * div > kMaxEntries) t = kMaxEntries / div;
-    if (const char *e = getenv("EPNET_RUNSUM_TILE")) {  // tuning: shorter tiles, more workgroups per CU
-        const long long cap = atoll(e);
-        if (cap >= kChunk && cap < t) t = cap;
-    }
     if (t >= row_floats) return (int)row_floats;   // one tile
     return (int)(t / kChunk * kChunk);             // whole chunks of 4096 positions (0: does not fit)
 }
@@ -495,7 +492,6 @@ inline int launch(int b, int c, int n, int div, int row_floats, const float *gra
     const size_t idx_stride = (size_t)row_floats * div;
     // parts: enough workgroups to spread the counting sort over the chip, each with at least a few hundred targets
     int parts = b >= 128 ? 2 : b >= 32 ? 8 : 16;
-    if (const char *e = getenv("EPNET_RUNSUM_PARTS")) parts = atoi(e) > 0 ? atoi(e) : parts;  // (tuning)
     while (parts > 1 && n / parts < 256) parts >>= 1;
     const int nb = div_up(n, parts);
     const int vec_out = ((n & 3) == 0 && ((uintptr_t)grad_points & 15) == 0) ? 1 : 0;

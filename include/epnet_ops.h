@@ -11,7 +11,8 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); all device entry
  *     points are asynchronous on that stream, allocate nothing, keep no state between calls and
  *     are re-entrant (the reference's ops are called concurrently from several host threads
- *     under nn.DataParallel, tools/train_rcnn.py:221-223);
+ *     under nn.DataParallel, tools/train_rcnn.py:221-223); the one process-wide setting, the
+ *     kernel-selection overrides of epnet_set_tuning, picks among kernels of identical results;
  *   - return value: EPNET_OK (0) or a negative EPNET_E* code; the library never calls exit()
  *     (the reference does: e.g. pointnet2_lib/pointnet2/src/ball_query_gpu.cu:62-65);
  *   - scratch memory is supplied by the caller (`*_workspace_bytes` + `workspace`), replacing
@@ -46,6 +47,21 @@ int epnet_abi_version(void);
 const char *epnet_strerror(int code);
 /* last HIP error string recorded by this thread's most recent failing call ("" if none) */
 const char *epnet_last_hip_error(void);
+
+/* kernel-selection overrides for tests and A/B measurements; names as the EPNET_* variables,
+   value -1 = the library's own choice. EPNET_EINVAL for an unknown name or a value out of range.
+   The table is seeded once, on first use, from the environment variables of the same names; an
+   override that does not fit a launch's shape is ignored there. No workspace size depends on it.
+     EPNET_FPS_PRUNE            0 | 1     0: brute-force FPS instead of the spatially pruned kernel
+     EPNET_FPS_PRUNE_MIN        >= 0      pruned FPS only above this many points (default 1024)
+     EPNET_FPS_PWAVES           4 | 8     waves of the self-sorting pruned FPS kernel
+     EPNET_FPS_WAVES            1 .. 16   waves of the register-resident FPS kernel (a power of two)
+     EPNET_BQ_PAIR              0 | 1     two centres per wave in the indexed ball query
+     EPNET_BQ_STREAM            0 | 1     streaming hit lists instead of the bitmap (paired query)
+     EPNET_BQ_ORDERED           0 | 1     centres served in their spatial order (epnet_ball_query_ordered)
+     EPNET_NN_TILE_MIN_BUCKETS  >= 0      bucket-of-unknowns three_nn from this many buckets (default 4096) */
+int epnet_set_tuning(const char *name, int value);
+int epnet_get_tuning(const char *name, int *value);
 
 /* ----------------------------------------------------------------------------------------
  * pointnet2 (pointnet2_lib/pointnet2/src/pointnet2_api.cpp:10-24)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""grad_bench.py -- the three run-sum gradient ops at bench_ops.py's shapes, alone (A/B of csrc/runsum.h variants:
-EPNET_RUNSUM_QUAD=0 selects the row-at-a-time kernel). One JSON line per op and shape; every result is checked against a
-float64 scatter-add of the same inputs first."""
+"""grad_bench.py -- the three run-sum gradient ops at bench_ops.py's shapes, alone (A/B of csrc/runsum.h variants: build one
+with profiles/micro/build_variants.sh and load it through EPNET_HIP_LIB). One JSON line per op and shape, naming the library
+it ran; every result is checked against a float64 scatter-add of the same inputs first."""
 import json
 import os
 import sys
@@ -9,7 +9,7 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import numpy as np
 import torch
-from epnet_amd import pointnet2_cuda as p2, synth
+from epnet_amd import _lib, pointnet2_cuda as p2, synth
 
 dev = torch.device("cuda:0")
 i32 = torch.int32
@@ -31,7 +31,7 @@ def timeit(fn, reps=30):
 
 def report(op, shape, ms, nbytes, err):
     print(json.dumps({"op": op, "shape": shape, "ms": round(ms, 4), "GBps": round(nbytes / (ms * 1e-3) / 1e9, 1), "max_err": err,
-                      "quad": os.environ.get("EPNET_RUNSUM_QUAD", "1")}), flush=True)
+                      "lib": os.path.basename(_lib.LIB_PATH)}), flush=True)
 
 
 def f64_scatter(terms, flat, m):   # terms (b, c, p), flat (b, p) -> (b, c, m)

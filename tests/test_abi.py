@@ -105,3 +105,86 @@ def test_scene_index_size_is_the_documented_layout(hiplib):
         return b * (np_ * 16 + (np_ // 64 + np_ // 256) * 24 + (np_ * 4 if n > 16384 else 0))
     for b, n in ((1, 1024), (3, 4096), (2, 16384), (2, 16385), (1, 40000), (4, 65536), (1, 1023), (1, 65537), (0, 4096)):
         assert hiplib.epnet_scene_index_bytes(b, n) == (want(b, n) if b > 0 else 0), (b, n)
+
+
+def test_tuning_round_trip_and_restore(hiplib):
+    """epnet_set_tuning / epnet_get_tuning: the kernel-selection overrides, -1 = the library's own choice"""
+    from epnet_amd import _lib
+    v = ctypes.c_int()
+    for name, value in (("EPNET_BQ_PAIR", 1), ("EPNET_BQ_PAIR", 0), ("EPNET_FPS_PWAVES", 8), ("EPNET_FPS_WAVES", 16),
+                        ("EPNET_FPS_PRUNE_MIN", 4096), ("EPNET_NN_TILE_MIN_BUCKETS", 1000000000)):
+        assert hiplib.epnet_get_tuning(name.encode(), ctypes.byref(v)) == 0
+        before = v.value
+        assert hiplib.epnet_set_tuning(name.encode(), value) == 0
+        assert hiplib.epnet_get_tuning(name.encode(), ctypes.byref(v)) == 0 and v.value == value
+        assert hiplib.epnet_set_tuning(name.encode(), -1) == 0
+        assert hiplib.epnet_get_tuning(name.encode(), ctypes.byref(v)) == 0 and v.value == -1
+        assert hiplib.epnet_set_tuning(name.encode(), before) == 0
+    with _lib.tuning(EPNET_BQ_STREAM=1, EPNET_FPS_PRUNE=0):
+        assert hiplib.epnet_get_tuning(b"EPNET_BQ_STREAM", ctypes.byref(v)) == 0 and v.value == 1
+        with pytest.raises(ZeroDivisionError):   # restored on the way out, also when the body raises
+            with _lib.tuning(EPNET_BQ_STREAM=0):
+                1 / 0
+        assert hiplib.epnet_get_tuning(b"EPNET_BQ_STREAM", ctypes.byref(v)) == 0 and v.value == 1
+    assert hiplib.epnet_get_tuning(b"EPNET_BQ_STREAM", ctypes.byref(v)) == 0 and v.value == -1
+    assert hiplib.epnet_get_tuning(b"EPNET_FPS_PRUNE", ctypes.byref(v)) == 0 and v.value == -1
+
+
+def test_tuning_rejects_unknown_names_and_values(hiplib):
+    from epnet_amd import _lib
+    v = ctypes.c_int(7)
+    einval = -1
+    for name in (b"EPNET_FPS_WIDE", b"EPNET_FPS_CTR", b"EPNET_FPS_BIG_WAVES", b"EPNET_BQ_PAD_KB", b"EPNET_GATHER_NO_QUAD",
+                 b"EPNET_RUNSUM_TILE", b"EPNET_RUNSUM_PARTS", b"EPNET_BQ_PAIRS", b"bq_pair", b""):
+        assert hiplib.epnet_set_tuning(name, 1) == einval, name
+        assert hiplib.epnet_get_tuning(name, ctypes.byref(v)) == einval, name
+    assert hiplib.epnet_set_tuning(None, 1) == einval and hiplib.epnet_get_tuning(b"EPNET_BQ_PAIR", None) == einval
+    for name, value in (("EPNET_BQ_PAIR", 2), ("EPNET_BQ_STREAM", -2), ("EPNET_BQ_ORDERED", 5), ("EPNET_FPS_PRUNE", 2),
+                        ("EPNET_FPS_PWAVES", 2), ("EPNET_FPS_PWAVES", 16), ("EPNET_FPS_WAVES", 3), ("EPNET_FPS_WAVES", 32),
+                        ("EPNET_FPS_WAVES", 0), ("EPNET_FPS_PRUNE_MIN", -5), ("EPNET_NN_TILE_MIN_BUCKETS", -2)):
+        assert hiplib.epnet_set_tuning(name.encode(), value) == einval, (name, value)
+    assert v.value == 7   # nothing written on failure
+    with pytest.raises(_lib.EpnetError, match="EPNET_FPS_WIDE"):
+        with _lib.tuning(EPNET_FPS_WIDE=1):
+            pass
+    with pytest.raises(_lib.EpnetError, match="EPNET_BQ_PAIR"):
+        with _lib.tuning(EPNET_BQ_STREAM=1, EPNET_BQ_PAIR=3):
+            pass
+    assert hiplib.epnet_get_tuning(b"EPNET_BQ_STREAM", ctypes.byref(v)) == 0 and v.value == -1   # the first one was undone
+
+
+def test_tuning_is_seeded_from_the_environment_once(hiplib):
+    """a process started with EPNET_BQ_PAIR=1 reads 1 back (what an A/B run of the unchanged bench.py relies on); a malformed
+    or out-of-range value is ignored"""
+    import subprocess
+    import sys
+    code = ("import ctypes; from epnet_amd import _lib; l = _lib.lib(); v = ctypes.c_int()\n"
+            "for name in ('EPNET_BQ_PAIR', 'EPNET_FPS_PWAVES', 'EPNET_FPS_PRUNE_MIN', 'EPNET_BQ_STREAM'):\n"
+            "    assert l.epnet_get_tuning(name.encode(), ctypes.byref(v)) == 0; print(name, v.value)\n")
+    env = dict(os.environ, EPNET_BQ_PAIR="1", EPNET_FPS_PWAVES="2", EPNET_FPS_PRUNE_MIN="4096x")
+    env.pop("EPNET_BQ_STREAM", None)
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.split("\n")[:4] == ["EPNET_BQ_PAIR 1", "EPNET_FPS_PWAVES -1", "EPNET_FPS_PRUNE_MIN -1", "EPNET_BQ_STREAM -1"]
+
+
+def test_library_reads_its_environment_in_one_place():
+    """no launcher calls getenv: the kernel-selection overrides are read once, by the table's seeding function in host.cpp, so a
+    workspace query and the launch it sizes cannot see different values, and a setenv elsewhere in the process cannot race a launch"""
+    csrc = os.path.join(ROOT, "epnet_amd", "csrc")
+    seen = {}
+    for f in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, f)).read()
+        if "getenv" in text:
+            seen[f] = text.count("getenv")
+    assert seen == {"host.cpp": 1}, seen
+    text = open(os.path.join(csrc, "host.cpp")).read()
+    start = text.index("bool seed_from_env()")
+    body_start = text.index("{", start)
+    depth, i = 0, body_start
+    while True:
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        if depth == 0:
+            break
+        i += 1
+    assert "getenv" in text[body_start:i]

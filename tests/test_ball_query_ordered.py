@@ -45,8 +45,10 @@ def _centres(oracle, xyz, m, how, seed):
 
 
 @pytest.fixture(autouse=True)
-def _force_the_ordered_kernels(monkeypatch):
-    monkeypatch.setenv("EPNET_BQ_ORDERED", "1")     # (by itself the library takes the order from 32768 points up only)
+def _force_the_ordered_kernels():
+    from epnet_amd import _lib
+    with _lib.tuning(EPNET_BQ_ORDERED=1):     # (by itself the library takes the order from 32768 points up only)
+        yield
 
 
 def _run(b, n, m, scales, xyz, centres):

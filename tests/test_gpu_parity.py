@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import golden
+from epnet_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -115,53 +116,41 @@ def test_fps_golden_fixtures():
 
 
 @pytest.mark.parametrize("env,n,m,kind", [
-    ({"EPNET_FPS_PRUNE": "0"}, 16384, 2048, "kitti"),      # brute force over 16 waves x 16 slots instead of the pruned kernel
-    ({"EPNET_FPS_PRUNE": "0"}, 4096, 1024, "dup"),
-    ({"EPNET_FPS_PRUNE": "0"}, 3000, 700, "kitti"),
-    ({"EPNET_FPS_PRUNE_MIN": "4096"}, 4096, 512, "kitti"),  # pruning only above 4096 points
-    ({"EPNET_FPS_PRUNE_MIN": "4096"}, 8192, 512, "dup"),
-    ({"EPNET_FPS_PWAVES": "2"}, 4096, 1024, "kitti"),       # wave counts of the self-sorting pruned kernel
-    ({"EPNET_FPS_PWAVES": "8"}, 4096, 1024, "dup"),
-    ({"EPNET_FPS_PWAVES": "4"}, 16384, 1024, "kitti"),
-    ({"EPNET_FPS_WAVES": "1"}, 1024, 256, "dup"),           # wave counts of the register-resident brute-force kernel
-    ({"EPNET_FPS_WAVES": "4"}, 1024, 256, "kitti"),
-    ({"EPNET_FPS_WAVES": "2"}, 512, 128, "dup"),
-    ({"EPNET_FPS_WIDE": "1"}, 16384, 2048, "kitti"),        # 16 waves x 16 slots over the scene index
-    ({"EPNET_FPS_WIDE": "1"}, 12000, 1500, "dup"),
-    ({"EPNET_FPS_CTR": "1"}, 16384, 2048, "kitti"),         # centres written by the sampling kernel itself, every layout
-    ({"EPNET_FPS_CTR": "1"}, 8192, 1024, "dup"),
-    ({"EPNET_FPS_CTR": "1"}, 4096, 1024, "kitti"),
-    ({"EPNET_FPS_CTR": "1"}, 2048, 512, "kitti"),
-    ({"EPNET_FPS_CTR": "1", "EPNET_FPS_WIDE": "1"}, 16384, 1024, "dup"),
-    ({"EPNET_FPS_BIG_WAVES": "4"}, 40000, 900, "kitti"),    # workgroup shapes of the big-scene kernel: 4 / 8 waves, 4 / 2 buckets per lane
-    ({"EPNET_FPS_BIG_WAVES": "8"}, 65536, 700, "dup"),
-    ({"EPNET_FPS_BIG_WAVES": "4"}, 20000, 1200, "dup"),
+    ({"EPNET_FPS_PRUNE": 0}, 16384, 2048, "kitti"),      # brute force over 16 waves x 16 slots instead of the pruned kernel
+    ({"EPNET_FPS_PRUNE": 0}, 4096, 1024, "dup"),
+    ({"EPNET_FPS_PRUNE": 0}, 3000, 700, "kitti"),
+    ({"EPNET_FPS_PRUNE_MIN": 4096}, 4096, 512, "kitti"),  # pruning only above 4096 points
+    ({"EPNET_FPS_PRUNE_MIN": 4096}, 8192, 512, "dup"),
+    ({"EPNET_FPS_PWAVES": 8}, 4096, 1024, "dup"),         # wave counts of the self-sorting pruned kernel
+    ({"EPNET_FPS_PWAVES": 4}, 16384, 1024, "kitti"),
+    ({"EPNET_FPS_WAVES": 1}, 1024, 256, "dup"),           # wave counts of the register-resident brute-force kernel
+    ({"EPNET_FPS_WAVES": 4}, 1024, 256, "kitti"),
+    ({"EPNET_FPS_WAVES": 2}, 512, 128, "dup"),
 ])
-def test_fps_tuning_variants_match_oracle(oracle, monkeypatch, env, n, m, kind):
-    """every kernel variant an EPNET_FPS_* variable selects (read per call) gives the oracle's indices, running
-    distances and centres: nothing in the product library is out of the tests' reach"""
+def test_fps_tuning_variants_match_oracle(oracle, env, n, m, kind):
+    """every kernel an EPNET_FPS_* override selects gives the oracle's indices, running distances and centres at shapes
+    where the library's own choice is another kernel: nothing in the product library is out of the tests' reach"""
     from epnet_amd import pointnet2_cuda as ext
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    b = 2
-    xyz = rand_cloud(b, n, seed=500 + n + m, kind=kind)
-    o_idx, o_temp = oracle.furthest_point_sampling(xyz, m, return_temp=True)
-    d_xyz = dev(xyz)
-    temp = torch.full((b, n), 1e10, device=DEV)
-    idx = torch.full((b, m), -1, dtype=torch.int32, device=DEV)
-    ext.furthest_point_sampling_wrapper(b, n, m, d_xyz, temp, idx)
-    np.testing.assert_array_equal(host(idx), o_idx)
-    np.testing.assert_array_equal(host(temp), o_temp)
-    index = ext.scene_index(d_xyz)
-    temp.fill_(1e10); idx.fill_(-1)
-    ext.furthest_point_sampling_indexed_wrapper(b, n, m, d_xyz, index, temp, idx)
-    np.testing.assert_array_equal(host(idx), o_idx)
-    np.testing.assert_array_equal(host(temp), o_temp)
-    idx.fill_(-1)
-    centres = torch.full((b, m, 3), float("nan"), device=DEV)
-    ext.sample_centres_wrapper(b, n, m, d_xyz, index, idx, centres)
-    np.testing.assert_array_equal(host(idx), o_idx)
-    np.testing.assert_array_equal(host(centres), np.take_along_axis(xyz, o_idx[:, :, None].astype(np.int64), axis=1))
+    with _lib.tuning(**env):
+        b = 2
+        xyz = rand_cloud(b, n, seed=500 + n + m, kind=kind)
+        o_idx, o_temp = oracle.furthest_point_sampling(xyz, m, return_temp=True)
+        d_xyz = dev(xyz)
+        temp = torch.full((b, n), 1e10, device=DEV)
+        idx = torch.full((b, m), -1, dtype=torch.int32, device=DEV)
+        ext.furthest_point_sampling_wrapper(b, n, m, d_xyz, temp, idx)
+        np.testing.assert_array_equal(host(idx), o_idx)
+        np.testing.assert_array_equal(host(temp), o_temp)
+        index = ext.scene_index(d_xyz)
+        temp.fill_(1e10); idx.fill_(-1)
+        ext.furthest_point_sampling_indexed_wrapper(b, n, m, d_xyz, index, temp, idx)
+        np.testing.assert_array_equal(host(idx), o_idx)
+        np.testing.assert_array_equal(host(temp), o_temp)
+        idx.fill_(-1)
+        centres = torch.full((b, m, 3), float("nan"), device=DEV)
+        ext.sample_centres_wrapper(b, n, m, d_xyz, index, idx, centres)
+        np.testing.assert_array_equal(host(idx), o_idx)
+        np.testing.assert_array_equal(host(centres), np.take_along_axis(xyz, o_idx[:, :, None].astype(np.int64), axis=1))
 
 
 def test_config1_fixture_on_the_gpu():
@@ -267,17 +256,17 @@ def test_fps_over_scene_index_ties(oracle):
     (1, 3000, 200, ((5.0, 100), (0.5, 3)), "ubox"),              # nsample beyond the 64-entry hit list
     (2, 2048, 1, ((1.0, 8), (2.0, 16)), "kitti"), (2, 2048, 3, ((1.0, 8), (2.0, 16)), "kitti"),   # odd tails of the pair kernel
 ])
-@pytest.mark.parametrize("pair", ["0", "1"])   # one / two centres per wave (the library picks by launch size)
-def test_ball_queries_of_an_msg_level_in_one_launch(oracle, b, n, m, scales, kind, pair, monkeypatch):
+@pytest.mark.parametrize("pair", [0, 1])   # one / two centres per wave (the library picks by launch size)
+def test_ball_queries_of_an_msg_level_in_one_launch(oracle, b, n, m, scales, kind, pair):
     from epnet_amd import pointnet2_cuda as ext
-    monkeypatch.setenv("EPNET_BQ_PAIR", pair)
-    xyz = rand_cloud(b, n, seed=700 + n, kind=kind)
-    centres = np.ascontiguousarray(xyz[:, :: max(1, n // m)][:, :m])
-    d_xyz, d_c = dev(xyz), dev(centres)
-    outs = [torch.full((b, m, ns), -5, dtype=torch.int32, device=DEV) for _r, ns in scales]
-    ext.ball_query_multi_wrapper(b, n, m, [r for r, _ in scales], [ns for _, ns in scales], d_c, d_xyz, ext.scene_index(d_xyz), outs)
-    for (r, ns), got in zip(scales, outs):
-        np.testing.assert_array_equal(host(got), oracle.ball_query(r, ns, xyz, centres))
+    with _lib.tuning(EPNET_BQ_PAIR=pair):
+        xyz = rand_cloud(b, n, seed=700 + n, kind=kind)
+        centres = np.ascontiguousarray(xyz[:, :: max(1, n // m)][:, :m])
+        d_xyz, d_c = dev(xyz), dev(centres)
+        outs = [torch.full((b, m, ns), -5, dtype=torch.int32, device=DEV) for _r, ns in scales]
+        ext.ball_query_multi_wrapper(b, n, m, [r for r, _ in scales], [ns for _, ns in scales], d_c, d_xyz, ext.scene_index(d_xyz), outs)
+        for (r, ns), got in zip(scales, outs):
+            np.testing.assert_array_equal(host(got), oracle.ball_query(r, ns, xyz, centres))
 
 
 def test_one_scene_index_serves_sampling_and_both_ball_queries(oracle):
@@ -313,16 +302,16 @@ def test_one_scene_index_serves_sampling_and_both_ball_queries(oracle):
     (1, 5000, 13, 100.0, 128, "ubox"),                                   # every ball saturates at once
     (1, 65536, 300, 0.5, 64, "kitti"), (1, 40000, 100, 0.8, 48, "kitti"),  # config-5 size: largest indexed path
 ])
-@pytest.mark.parametrize("pair", ["0", "1"])
-def test_ball_query_matches_oracle(oracle, b, n, m, radius, ns, kind, pair, monkeypatch):
-    monkeypatch.setenv("EPNET_BQ_PAIR", pair)
+@pytest.mark.parametrize("pair", [0, 1])
+def test_ball_query_matches_oracle(oracle, b, n, m, radius, ns, kind, pair):
     from epnet_amd import pointnet2_utils as p2u
-    xyz = rand_cloud(b, n, seed=200 + n + m, kind=kind)
-    centres = np.ascontiguousarray(xyz[:, np.random.default_rng(n).permutation(n)[:m]])
-    if kind == "ubox":
-        centres[:, -1] = 1e4  # one empty ball per scene -> all-zero row
-    got = host(p2u.ball_query(radius, ns, dev(xyz), dev(centres)))
-    np.testing.assert_array_equal(got, oracle.ball_query(radius, ns, xyz, centres))
+    with _lib.tuning(EPNET_BQ_PAIR=pair):
+        xyz = rand_cloud(b, n, seed=200 + n + m, kind=kind)
+        centres = np.ascontiguousarray(xyz[:, np.random.default_rng(n).permutation(n)[:m]])
+        if kind == "ubox":
+            centres[:, -1] = 1e4  # one empty ball per scene -> all-zero row
+        got = host(p2u.ball_query(radius, ns, dev(xyz), dev(centres)))
+        np.testing.assert_array_equal(got, oracle.ball_query(radius, ns, xyz, centres))
 
 
 def test_ball_query_writes_every_slot_and_boundary_is_strict(oracle):
@@ -336,34 +325,33 @@ def test_ball_query_writes_every_slot_and_boundary_is_strict(oracle):
 
 
 @pytest.mark.parametrize("n,order", [(16384, "descending"), (16384, "ascending"), (16384, "random"), (2048, "descending"), (65536, "descending")])
-@pytest.mark.parametrize("pair,stream", [("0", "0"), ("1", "0"), ("1", "1")])
-def test_ball_query_crowded_lists_keep_the_smallest_indices(oracle, n, order, pair, stream, monkeypatch):
+@pytest.mark.parametrize("pair,stream", [(0, 0), (1, 0), (1, 1)])
+def test_ball_query_crowded_lists_keep_the_smallest_indices(oracle, n, order, pair, stream):
     """balls that hold thousands of points. The streaming variant of the pair kernel (the library's choice above 16384 points,
     forced here on every size) cuts a hit list that runs full during the walk down to its nsample smallest ORIGINAL indices, again
     and again, with a threshold for what the list takes afterwards; the other kernels walk a second time through a bitmap.
     `descending`: the walk (cell order: along x) meets the largest indices first, so every cut replaces the whole list;
     `ascending`: the first cut already holds the answer; nsample 1 .. 64, and 100 (beyond a list: always the bitmap pass)"""
     from epnet_amd import pointnet2_cuda as ext
-    monkeypatch.setenv("EPNET_BQ_PAIR", pair)
-    monkeypatch.setenv("EPNET_BQ_STREAM", stream)
-    rng = np.random.default_rng(n)
-    xyz = (rng.random((1, n, 3)) * np.array([40.0, 1.0, 1.0])).astype(np.float32)
-    perm = {"ascending": np.argsort(xyz[0, :, 0]), "descending": np.argsort(-xyz[0, :, 0]), "random": rng.permutation(n)}[order]
-    xyz = np.ascontiguousarray(xyz[:, perm])
-    m = 37
-    centres = np.ascontiguousarray(xyz[:, rng.permutation(n)[:m]])
-    centres[0, -1] = (20.0, 0.5, 0.5)
-    d_xyz, d_c = dev(xyz), dev(centres)
-    index = ext.scene_index(d_xyz)
-    scales = ((6.0, 64), (9.0, 1)), ((3.0, 5), (50.0, 33)), ((7.0, 100), (2.0, 64))
-    for sc in scales:
-        outs = [torch.full((1, m, ns), -5, dtype=torch.int32, device=DEV) for _r, ns in sc]
-        ext.ball_query_multi_wrapper(1, n, m, [r for r, _ in sc], [ns for _, ns in sc], d_c, d_xyz, index, outs)
-        for (r, ns), got in zip(sc, outs):
-            want = oracle.ball_query(r, ns, xyz, centres)
-            np.testing.assert_array_equal(host(got), want)
-    hits = (np.linalg.norm(xyz[0][None] - centres[0][:, None], axis=-1) < 6.0).sum(1)
-    assert hits.min() > (512 if n >= 16384 else 256)                   # every ball overflows the longest list of its kernel
+    with _lib.tuning(EPNET_BQ_PAIR=pair, EPNET_BQ_STREAM=stream):
+        rng = np.random.default_rng(n)
+        xyz = (rng.random((1, n, 3)) * np.array([40.0, 1.0, 1.0])).astype(np.float32)
+        perm = {"ascending": np.argsort(xyz[0, :, 0]), "descending": np.argsort(-xyz[0, :, 0]), "random": rng.permutation(n)}[order]
+        xyz = np.ascontiguousarray(xyz[:, perm])
+        m = 37
+        centres = np.ascontiguousarray(xyz[:, rng.permutation(n)[:m]])
+        centres[0, -1] = (20.0, 0.5, 0.5)
+        d_xyz, d_c = dev(xyz), dev(centres)
+        index = ext.scene_index(d_xyz)
+        scales = ((6.0, 64), (9.0, 1)), ((3.0, 5), (50.0, 33)), ((7.0, 100), (2.0, 64))
+        for sc in scales:
+            outs = [torch.full((1, m, ns), -5, dtype=torch.int32, device=DEV) for _r, ns in sc]
+            ext.ball_query_multi_wrapper(1, n, m, [r for r, _ in sc], [ns for _, ns in sc], d_c, d_xyz, index, outs)
+            for (r, ns), got in zip(sc, outs):
+                want = oracle.ball_query(r, ns, xyz, centres)
+                np.testing.assert_array_equal(host(got), want)
+        hits = (np.linalg.norm(xyz[0][None] - centres[0][:, None], axis=-1) < 6.0).sum(1)
+        assert hits.min() > (512 if n >= 16384 else 256)                   # every ball overflows the longest list of its kernel
 
 
 def test_ball_query_indexed_and_direct_paths_agree(oracle):
@@ -601,59 +589,59 @@ def test_three_nn_indexed_and_direct_paths_agree(oracle):
     (2, 700, 1100, "kitti"),      # unknown set below the indexed range: known-index-only kernel
     (2, 3000, 300, "kitti"),      # known set below it: plain path
 ])
-def test_three_nn_over_scene_indices_matches_oracle(oracle, b, n, m, kind, monkeypatch):
+def test_three_nn_over_scene_indices_matches_oracle(oracle, b, n, m, kind):
     """epnet_three_nn_indexed with both point sets indexed (one wave per unknown bucket), with the known set only,
     and with neither: indices and squared distances bit-equal to the oracle"""
     from epnet_amd import pointnet2_cuda as ext
-    monkeypatch.setenv("EPNET_NN_TILE_MIN_BUCKETS", "1")   # the library keeps the bucket kernel for big launches only
-    unknown = rand_cloud(b, n, seed=n + 1, kind=kind)
-    known = rand_cloud(b, m, seed=m + 2, kind=kind)
-    if kind == "dup":
-        known[:, 100:160] = unknown[:, :60]   # exact zero distances and ties between equal known rows
-    d_u, d_k = dev(unknown), dev(known)
-    o_d2, o_i = oracle.three_nn(unknown, known)
-    ui, ki = ext.scene_index(d_u), ext.scene_index(d_k)
-    for use_u in (True, False):
-        d2 = torch.full((b, n, 3), -1.0, device=DEV)
-        i = torch.full((b, n, 3), -1, dtype=torch.int32, device=DEV)
-        ext.three_nn_indexed_wrapper(b, n, m, d_u, d_k, ui if use_u else None, ki, d2, i)
-        np.testing.assert_array_equal(host(i), o_i)
-        np.testing.assert_array_equal(host(d2), o_d2)
+    with _lib.tuning(EPNET_NN_TILE_MIN_BUCKETS=1):   # the library keeps the bucket kernel for big launches only
+        unknown = rand_cloud(b, n, seed=n + 1, kind=kind)
+        known = rand_cloud(b, m, seed=m + 2, kind=kind)
+        if kind == "dup":
+            known[:, 100:160] = unknown[:, :60]   # exact zero distances and ties between equal known rows
+        d_u, d_k = dev(unknown), dev(known)
+        o_d2, o_i = oracle.three_nn(unknown, known)
+        ui, ki = ext.scene_index(d_u), ext.scene_index(d_k)
+        for use_u in (True, False):
+            d2 = torch.full((b, n, 3), -1.0, device=DEV)
+            i = torch.full((b, n, 3), -1, dtype=torch.int32, device=DEV)
+            ext.three_nn_indexed_wrapper(b, n, m, d_u, d_k, ui if use_u else None, ki, d2, i)
+            np.testing.assert_array_equal(host(i), o_i)
+            np.testing.assert_array_equal(host(d2), o_d2)
 
 
 @pytest.mark.parametrize("tile", [True, False])
-def test_three_nn_non_finite_coordinates(oracle, tile, monkeypatch):
+def test_three_nn_non_finite_coordinates(oracle, tile):
     """NaN (either sign bit) and +-inf coordinates on both sides: the reference takes a point only if `d < best` with best starting
     at (float)1e40 = +inf (interpolate_gpu.cu:30-48), so a distance of +inf or NaN never enters a list -- unknowns with a
     non-finite coordinate get (inf, 0) three times, known points with one are never anybody's neighbour. The bucket kernel
     orders its (d, k) keys as doubles: a NaN of either sign must stay out of that order."""
     from epnet_amd import pointnet2_cuda as ext
-    monkeypatch.setenv("EPNET_NN_TILE_MIN_BUCKETS", "1" if tile else "1000000000")
-    b, n, m = 2, 4096, 1536
-    unknown = rand_cloud(b, n, seed=21, kind="kitti")
-    known = rand_cloud(b, m, seed=22, kind="kitti")
-    neg_nan = np.frombuffer(np.uint32(0xFFC00000).tobytes(), dtype=np.float32)[0]
-    # NaN payloads propagate through the subtraction and the squares: the distance of such a point carries them, and bits from
-    # 0x7FF00000 up are a NaN as the high word of a double as well (ADVICE r02: the canonical 0x7FC00000 alone cannot show that)
-    bad_bits = [0x7FC00000, 0xFFC00000, 0x7F800000, 0xFF800000, 0x7FFFFFFF, 0xFFFFFFFF, 0x7FF00001, 0xFFF80000]
-    rng = np.random.default_rng(5)
-    for arr, count in ((known, 64), (unknown, 96)):
-        bits = arr.view(np.uint32)          # (written as bit patterns: no float move may quieten or canonicalise them)
-        for k in range(count):
-            bits[rng.integers(0, b), rng.integers(0, arr.shape[1]), rng.integers(0, 3)] = bad_bits[k % len(bad_bits)]
-    known[1, 7] = [neg_nan, neg_nan, neg_nan]
-    known.view(np.uint32)[1, 9] = [0x7FFFFFFF, 0xFFFFFFFF, 0x7FFFFFFF]
-    unknown[0, 11] = [np.float32(np.inf), np.float32(-np.inf), neg_nan]
-    unknown.view(np.uint32)[0, 13] = [0xFFFFFFFF, 0x7FFFFFFF, 0x7FF00001]
-    d_u, d_k = dev(unknown), dev(known)
-    o_d2, o_i = oracle.three_nn(unknown, known)
-    assert np.isinf(o_d2).any() and np.isfinite(o_d2).any()
-    ui, ki = ext.scene_index(d_u), ext.scene_index(d_k)
-    d2 = torch.full((b, n, 3), -1.0, device=DEV)
-    i = torch.full((b, n, 3), -1, dtype=torch.int32, device=DEV)
-    ext.three_nn_indexed_wrapper(b, n, m, d_u, d_k, ui, ki, d2, i)
-    np.testing.assert_array_equal(host(i), o_i)
-    np.testing.assert_array_equal(host(d2), o_d2)
+    with _lib.tuning(EPNET_NN_TILE_MIN_BUCKETS=1 if tile else 1000000000):
+        b, n, m = 2, 4096, 1536
+        unknown = rand_cloud(b, n, seed=21, kind="kitti")
+        known = rand_cloud(b, m, seed=22, kind="kitti")
+        neg_nan = np.frombuffer(np.uint32(0xFFC00000).tobytes(), dtype=np.float32)[0]
+        # NaN payloads propagate through the subtraction and the squares: the distance of such a point carries them, and bits from
+        # 0x7FF00000 up are a NaN as the high word of a double as well (ADVICE r02: the canonical 0x7FC00000 alone cannot show that)
+        bad_bits = [0x7FC00000, 0xFFC00000, 0x7F800000, 0xFF800000, 0x7FFFFFFF, 0xFFFFFFFF, 0x7FF00001, 0xFFF80000]
+        rng = np.random.default_rng(5)
+        for arr, count in ((known, 64), (unknown, 96)):
+            bits = arr.view(np.uint32)          # (written as bit patterns: no float move may quieten or canonicalise them)
+            for k in range(count):
+                bits[rng.integers(0, b), rng.integers(0, arr.shape[1]), rng.integers(0, 3)] = bad_bits[k % len(bad_bits)]
+        known[1, 7] = [neg_nan, neg_nan, neg_nan]
+        known.view(np.uint32)[1, 9] = [0x7FFFFFFF, 0xFFFFFFFF, 0x7FFFFFFF]
+        unknown[0, 11] = [np.float32(np.inf), np.float32(-np.inf), neg_nan]
+        unknown.view(np.uint32)[0, 13] = [0xFFFFFFFF, 0x7FFFFFFF, 0x7FF00001]
+        d_u, d_k = dev(unknown), dev(known)
+        o_d2, o_i = oracle.three_nn(unknown, known)
+        assert np.isinf(o_d2).any() and np.isfinite(o_d2).any()
+        ui, ki = ext.scene_index(d_u), ext.scene_index(d_k)
+        d2 = torch.full((b, n, 3), -1.0, device=DEV)
+        i = torch.full((b, n, 3), -1, dtype=torch.int32, device=DEV)
+        ext.three_nn_indexed_wrapper(b, n, m, d_u, d_k, ui, ki, d2, i)
+        np.testing.assert_array_equal(host(i), o_i)
+        np.testing.assert_array_equal(host(d2), o_d2)
 
 
 @pytest.mark.parametrize("b,n_src,n", [(2, 16384, 4096), (3, 4096, 1024), (2, 5000, 2500), (1, 20000, 16384)])

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from epnet_amd import _lib
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -128,19 +130,19 @@ def test_sweep_furthest_point_sampling(oracle, case, b, n, m, kind):
 
 
 @pytest.mark.parametrize("case,b,n,m,kind", _cases(96, 12, 65536))
-@pytest.mark.parametrize("pair", ["0", "1"])
-def test_sweep_ball_query(oracle, case, b, n, m, kind, pair, monkeypatch):
+@pytest.mark.parametrize("pair", [0, 1])
+def test_sweep_ball_query(oracle, case, b, n, m, kind, pair):
     from epnet_amd import pointnet2_utils as p2u
-    monkeypatch.setenv("EPNET_BQ_PAIR", pair)
-    rng = np.random.default_rng(5000 + case)
-    m = min(m, 600)
-    xyz = cloud(kind, b, n, seed=2000 + case)
-    extent = float(np.ptp(xyz[0], axis=0).max()) or 1.0
-    radius = float(np.exp(rng.uniform(np.log(extent / 300.0), np.log(extent * 1.5))))
-    ns = int(rng.choice([1, 2, 5, 16, 32, 63, 64, 65, 100]))
-    centres = np.ascontiguousarray(xyz[:, rng.permutation(n)[:m]] + (rng.random((b, m, 3)) < 0.3) * rng.normal(0, radius / 2, (b, m, 3))).astype(np.float32)
-    got = host(p2u.ball_query(radius, ns, dev(xyz), dev(centres)))
-    np.testing.assert_array_equal(got, oracle.ball_query(radius, ns, xyz, centres))
+    with _lib.tuning(EPNET_BQ_PAIR=pair):
+        rng = np.random.default_rng(5000 + case)
+        m = min(m, 600)
+        xyz = cloud(kind, b, n, seed=2000 + case)
+        extent = float(np.ptp(xyz[0], axis=0).max()) or 1.0
+        radius = float(np.exp(rng.uniform(np.log(extent / 300.0), np.log(extent * 1.5))))
+        ns = int(rng.choice([1, 2, 5, 16, 32, 63, 64, 65, 100]))
+        centres = np.ascontiguousarray(xyz[:, rng.permutation(n)[:m]] + (rng.random((b, m, 3)) < 0.3) * rng.normal(0, radius / 2, (b, m, 3))).astype(np.float32)
+        got = host(p2u.ball_query(radius, ns, dev(xyz), dev(centres)))
+        np.testing.assert_array_equal(got, oracle.ball_query(radius, ns, xyz, centres))
 
 
 @pytest.mark.parametrize("case,b,n,m,kind", _cases(64, 13, 40000))
@@ -260,27 +262,27 @@ def test_sweep_query_and_group(oracle, case, b, n, m, kind):
 
 
 @pytest.mark.parametrize("case,b,n,m,kind", _cases(40, 17, 40000))
-@pytest.mark.parametrize("tile", ["1", "1000000000"])
-def test_sweep_three_nn_over_scene_indices(oracle, case, b, n, m, kind, tile, monkeypatch):
+@pytest.mark.parametrize("tile", [1, 1000000000])
+def test_sweep_three_nn_over_scene_indices(oracle, case, b, n, m, kind, tile):
     """epnet_three_nn_indexed: a wave per bucket of unknowns (forced with EPNET_NN_TILE_MIN_BUCKETS=1) or per unknown, over the scene
     indices of whichever of the two sets has one"""
     from epnet_amd import pointnet2_cuda as ext
-    monkeypatch.setenv("EPNET_NN_TILE_MIN_BUCKETS", tile)
-    rng = np.random.default_rng(13000 + case)
-    m = max(m, int(rng.choice([1, 1024, 1100, 2259, 4096])))
-    unknown = cloud(kind, b, n, seed=9000 + case)
-    known = cloud(KINDS[(case + 2) % len(KINDS)], b, m, seed=9500 + case)
-    if m >= 8 and n >= 8:
-        known[:, :4] = unknown[:, :4]          # exact zero distances
-        known[:, 4:8] = known[:, :4]           # ... and ties between equal known rows
-    d_u, d_k = dev(unknown), dev(known)
-    o_d2, o_i = oracle.three_nn(unknown, known)
-    ui, ki = ext.scene_index(d_u), ext.scene_index(d_k)
-    d2 = out_tensor((b, n, 3), torch.float32, -1.0)
-    i = out_tensor((b, n, 3), torch.int32, -1)
-    ext.three_nn_indexed_wrapper(b, n, m, d_u, d_k, ui, ki, d2, i)
-    np.testing.assert_array_equal(host(i), o_i)
-    np.testing.assert_array_equal(host(d2), o_d2)
+    with _lib.tuning(EPNET_NN_TILE_MIN_BUCKETS=tile):
+        rng = np.random.default_rng(13000 + case)
+        m = max(m, int(rng.choice([1, 1024, 1100, 2259, 4096])))
+        unknown = cloud(kind, b, n, seed=9000 + case)
+        known = cloud(KINDS[(case + 2) % len(KINDS)], b, m, seed=9500 + case)
+        if m >= 8 and n >= 8:
+            known[:, :4] = unknown[:, :4]          # exact zero distances
+            known[:, 4:8] = known[:, :4]           # ... and ties between equal known rows
+        d_u, d_k = dev(unknown), dev(known)
+        o_d2, o_i = oracle.three_nn(unknown, known)
+        ui, ki = ext.scene_index(d_u), ext.scene_index(d_k)
+        d2 = out_tensor((b, n, 3), torch.float32, -1.0)
+        i = out_tensor((b, n, 3), torch.int32, -1)
+        ext.three_nn_indexed_wrapper(b, n, m, d_u, d_k, ui, ki, d2, i)
+        np.testing.assert_array_equal(host(i), o_i)
+        np.testing.assert_array_equal(host(d2), o_d2)
 
 
 def _pool_cases(count, seed):
@@ -335,52 +337,52 @@ def test_sweep_nms_and_iou(oracle, case):
 
 
 @pytest.mark.parametrize("case,b,n,m,kind", _cases(48, 19, 65536))
-@pytest.mark.parametrize("pair", ["0", "1"])
-def test_sweep_msg_level(oracle, case, b, n, m, kind, pair, monkeypatch):
+@pytest.mark.parametrize("pair", [0, 1])
+def test_sweep_msg_level(oracle, case, b, n, m, kind, pair):
     """one MSG level as the SA stack issues it: the ball queries of all scales in one launch (centre order and the centres' own
     spatial order), the groupings of all scales in one call, the neighbourhood max-pool -- 1 to 3 scales, nested or not"""
     from epnet_amd import pointnet2_cuda as ext
-    monkeypatch.setenv("EPNET_BQ_PAIR", pair)
-    rng = np.random.default_rng(15000 + case)
-    if n < 1024:
-        n = int(rng.choice([1024, 1500, 2048, 2049]))          # (the multi-scale entry points take a scene index)
-    m = int(min(m, 400, n))
-    k = int(rng.integers(1, 4))
-    c = int(rng.choice([0, 4, 16, 19, 64]))
-    xyz = cloud(kind, b, n, seed=10000 + case)
-    extent = float(np.ptp(xyz[0], axis=0).max()) or 1.0
-    radii = [float(np.exp(rng.uniform(np.log(extent / 200.0), np.log(extent)))) for _ in range(k)]
-    nss = [int(rng.choice([1, 4, 8, 16, 32, 64, 72])) for _ in range(k)]
-    centres = np.ascontiguousarray(xyz[:, rng.permutation(n)[:m]])
-    d_xyz, d_c = dev(xyz), dev(centres)
-    index = ext.scene_index(d_xyz)
-    want = [oracle.ball_query(r, ns, xyz, centres) for r, ns in zip(radii, nss)]
-    outs = [out_tensor((b, m, ns), torch.int32, -5) for ns in nss]
-    ext.ball_query_multi_wrapper(b, n, m, radii, nss, d_c, d_xyz, index, outs)
-    for got, w in zip(outs, want):
-        np.testing.assert_array_equal(host(got), w)
-    ci = ext.scene_index(d_c)                                     # None below 1024 centres: the wrapper falls back
-    outs2 = [out_tensor((b, m, ns), torch.int32, -5) for ns in nss]
-    ext.ball_query_ordered_wrapper(b, n, m, radii, nss, d_c, d_xyz, index, ci, outs2)
-    for got, w in zip(outs2, want):
-        np.testing.assert_array_equal(host(got), w)
-    feats = rng.standard_normal((b, c, n)).astype(np.float32) if c else None
-    grouped = [out_tensor((b, 3 + c, m, ns), torch.float32, float("nan")) for ns in nss]
-    ext.group_concat_multi_wrapper(b, c, n, m, nss, d_xyz, d_c, dev(feats) if c else None, outs, grouped, True)
-    xyz_t = np.ascontiguousarray(xyz.transpose(0, 2, 1))
-    for got, w in zip(grouped, want):
-        parts = [oracle.group_points(xyz_t, w) - centres.transpose(0, 2, 1)[..., None]]
-        if c:
-            parts.append(oracle.group_points(feats, w))
-        ref = np.concatenate(parts, axis=1)
-        np.testing.assert_array_equal(host(got), ref)
-        rows, ns = ref.shape[0] * ref.shape[1] * ref.shape[2], ref.shape[3]
-        pooled = out_tensor((rows,))
-        arg = out_tensor((rows,), torch.int32)
-        ext.pool_max_wrapper(rows, ns, got, pooled, arg)
-        o_max, o_arg = oracle.pool_max(ref)
-        np.testing.assert_array_equal(host(pooled), o_max.reshape(-1))
-        np.testing.assert_array_equal(host(arg), o_arg.reshape(-1))
+    with _lib.tuning(EPNET_BQ_PAIR=pair):
+        rng = np.random.default_rng(15000 + case)
+        if n < 1024:
+            n = int(rng.choice([1024, 1500, 2048, 2049]))          # (the multi-scale entry points take a scene index)
+        m = int(min(m, 400, n))
+        k = int(rng.integers(1, 4))
+        c = int(rng.choice([0, 4, 16, 19, 64]))
+        xyz = cloud(kind, b, n, seed=10000 + case)
+        extent = float(np.ptp(xyz[0], axis=0).max()) or 1.0
+        radii = [float(np.exp(rng.uniform(np.log(extent / 200.0), np.log(extent)))) for _ in range(k)]
+        nss = [int(rng.choice([1, 4, 8, 16, 32, 64, 72])) for _ in range(k)]
+        centres = np.ascontiguousarray(xyz[:, rng.permutation(n)[:m]])
+        d_xyz, d_c = dev(xyz), dev(centres)
+        index = ext.scene_index(d_xyz)
+        want = [oracle.ball_query(r, ns, xyz, centres) for r, ns in zip(radii, nss)]
+        outs = [out_tensor((b, m, ns), torch.int32, -5) for ns in nss]
+        ext.ball_query_multi_wrapper(b, n, m, radii, nss, d_c, d_xyz, index, outs)
+        for got, w in zip(outs, want):
+            np.testing.assert_array_equal(host(got), w)
+        ci = ext.scene_index(d_c)                                     # None below 1024 centres: the wrapper falls back
+        outs2 = [out_tensor((b, m, ns), torch.int32, -5) for ns in nss]
+        ext.ball_query_ordered_wrapper(b, n, m, radii, nss, d_c, d_xyz, index, ci, outs2)
+        for got, w in zip(outs2, want):
+            np.testing.assert_array_equal(host(got), w)
+        feats = rng.standard_normal((b, c, n)).astype(np.float32) if c else None
+        grouped = [out_tensor((b, 3 + c, m, ns), torch.float32, float("nan")) for ns in nss]
+        ext.group_concat_multi_wrapper(b, c, n, m, nss, d_xyz, d_c, dev(feats) if c else None, outs, grouped, True)
+        xyz_t = np.ascontiguousarray(xyz.transpose(0, 2, 1))
+        for got, w in zip(grouped, want):
+            parts = [oracle.group_points(xyz_t, w) - centres.transpose(0, 2, 1)[..., None]]
+            if c:
+                parts.append(oracle.group_points(feats, w))
+            ref = np.concatenate(parts, axis=1)
+            np.testing.assert_array_equal(host(got), ref)
+            rows, ns = ref.shape[0] * ref.shape[1] * ref.shape[2], ref.shape[3]
+            pooled = out_tensor((rows,))
+            arg = out_tensor((rows,), torch.int32)
+            ext.pool_max_wrapper(rows, ns, got, pooled, arg)
+            o_max, o_arg = oracle.pool_max(ref)
+            np.testing.assert_array_equal(host(pooled), o_max.reshape(-1))
+            np.testing.assert_array_equal(host(arg), o_arg.reshape(-1))
 
 
 def _scene_cases(count, seed):
