@@ -51,6 +51,18 @@ SIGNATURES = {
     "epnet_group_linear_grad_w": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_feature_gather": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_feature_gather_grad": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "epnet_gather_points_grad_det_workspace_bytes": (_sz, [_i, _i, _i]),
+    "epnet_gather_points_grad_det": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "epnet_group_points_grad_det_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "epnet_group_points_grad_det": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "epnet_group_concat_grad_det_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "epnet_group_concat_grad_det": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "epnet_three_interpolate_grad_det_workspace_bytes": (_sz, [_i, _i, _i]),
+    "epnet_three_interpolate_grad_det": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "epnet_feature_gather_grad_det_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "epnet_feature_gather_grad_det": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "epnet_group_linear_grad_w_det_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "epnet_group_linear_grad_w_det": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "epnet_pool_max": (_i, [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp]),
     "epnet_pool_max_grad": (_i, [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp]),
     "epnet_scene_index_bytes": (_sz, [_i, _i]),

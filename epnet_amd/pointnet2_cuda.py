@@ -14,6 +14,18 @@ from ._tensor import dev_ptr, need, on_device_of, writes
 _F, _I = torch.float32, torch.int32
 
 
+def _deterministic():
+    """torch.use_deterministic_algorithms(True): the gradients then take the *_det entry points (include/epnet_ops.h),
+    whose bits depend on the inputs and the shape alone -- the oracle's sequential order for the scatter-adds"""
+    return torch.are_deterministic_algorithms_enabled()
+
+
+def _det_call(l, name, ws_bytes, like, args, s, what):
+    """run epnet_<name>_det with scratch from torch's caching allocator; a shape it cannot run raises (no atomic fallback)"""
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=like.device)
+    _lib.check(getattr(l, "epnet_%s_det" % name)(*args, ws.data_ptr(), int(ws_bytes), s), "%s (deterministic)" % what)
+
+
 @writes("idx")
 def ball_query_wrapper(b, n, m, radius, nsample, new_xyz, xyz, idx):
     """ball_query_wrapper_fast, pointnet2_lib/pointnet2/src/ball_query.cpp:14-25"""
@@ -47,6 +59,11 @@ def group_points_grad_wrapper(b, c, n, npoints, nsample, grad_out, idx, grad_poi
     need(grad_out, b * c * npoints * nsample, "grad_out"); need(idx, b * npoints * nsample, "idx")
     need(grad_points, b * c * n, "grad_points")
     l = _lib.lib()
+    if _deterministic():
+        with on_device_of(grad_out) as s:
+            _det_call(l, "group_points_grad", l.epnet_group_points_grad_det_workspace_bytes(b, n, npoints, nsample), grad_out,
+                      (b, c, n, npoints, nsample, pg, pi, pp), s, "group_points_grad")
+        return 1
     ws_bytes = l.epnet_group_points_grad_workspace_bytes(b, n, npoints, nsample)
     with on_device_of(grad_out) as s:
         if ws_bytes:
@@ -73,6 +90,12 @@ def gather_points_grad_wrapper(b, c, n, npoints, grad_out, idx, grad_points):
     """gather_points_grad_wrapper_fast, sampling.cpp:23-33"""
     pg, pi, pp = dev_ptr(grad_out, "grad_out", _F), dev_ptr(idx, "idx", _I), dev_ptr(grad_points, "grad_points", _F)
     need(grad_out, b * c * npoints, "grad_out"); need(idx, b * npoints, "idx"); need(grad_points, b * c * n, "grad_points")
+    if _deterministic():
+        l = _lib.lib()
+        with on_device_of(grad_out) as s:
+            _det_call(l, "gather_points_grad", l.epnet_gather_points_grad_det_workspace_bytes(b, n, npoints), grad_out,
+                      (b, c, n, npoints, pg, pi, pp), s, "gather_points_grad")
+        return 1
     with on_device_of(grad_out) as s:
         _lib.check(_lib.lib().epnet_gather_points_grad(b, c, n, npoints, pg, pi, pp, s), "gather_points_grad")
     return 1
@@ -130,6 +153,11 @@ def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_point
     need(grad_out, b * c * n, "grad_out"); need(idx, b * n * 3, "idx"); need(weight, b * n * 3, "weight")
     need(grad_points, b * c * m, "grad_points")
     l = _lib.lib()
+    if _deterministic():
+        with on_device_of(grad_out) as s:
+            _det_call(l, "three_interpolate_grad", l.epnet_three_interpolate_grad_det_workspace_bytes(b, n, m), grad_out,
+                      (b, c, n, m, pg, pi, pw, pp), s, "three_interpolate_grad")
+        return
     ws_bytes = l.epnet_three_interpolate_grad_workspace_bytes(b, n, m)
     with on_device_of(grad_out) as s:
         if ws_bytes:
@@ -374,6 +402,11 @@ def group_concat_grad_wrapper(b, c, n, npoints, nsample, grad_out, idx, grad_fea
     pg, pi, pp = dev_ptr(grad_out, "grad_out", _F), dev_ptr(idx, "idx", _I), dev_ptr(grad_features, "grad_features", _F)
     need(grad_out, b * ((3 if use_xyz else 0) + c) * npoints * nsample, "grad_out"); need(grad_features, b * c * n, "grad_features")
     l = _lib.lib()
+    if _deterministic():
+        with on_device_of(grad_out) as s:
+            _det_call(l, "group_concat_grad", l.epnet_group_concat_grad_det_workspace_bytes(b, n, npoints, nsample), grad_out,
+                      (b, c, n, npoints, nsample, pg, pi, pp, int(bool(use_xyz))), s, "group_concat_grad")
+        return 1
     ws_bytes = l.epnet_group_points_grad_workspace_bytes(b, n, npoints, nsample)
     with on_device_of(grad_out) as s:
         if ws_bytes:
@@ -428,11 +461,18 @@ def group_linear_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, z, idx, w_xyz,
 
 @writes("grad_w")
 def group_linear_grad_w_wrapper(b, c, n, npoints, nsample, grad_out, xyz, new_xyz, idx, grad_w):
-    """grad_w (c,3), zero-filled by the caller, += sum of grad_out[b,co,m,s] * (xyz[idx] - centre)[k]"""
+    """grad_w (c,3), zero-filled by the caller, += sum of grad_out[b,co,m,s] * (xyz[idx] - centre)[k]
+    (under torch.use_deterministic_algorithms(True): in the fixed order of epnet_group_linear_grad_w_det)"""
     pg, px, pn = dev_ptr(grad_out, "grad_out", _F), dev_ptr(xyz, "xyz", _F), dev_ptr(new_xyz, "new_xyz", _F)
     pi, pw = dev_ptr(idx, "idx", _I), dev_ptr(grad_w, "grad_w", _F)
     need(grad_out, b * c * npoints * nsample, "grad_out"); need(xyz, b * n * 3, "xyz"); need(new_xyz, b * npoints * 3, "new_xyz")
     need(idx, b * npoints * nsample, "idx"); need(grad_w, c * 3, "grad_w")
+    if _deterministic():
+        l = _lib.lib()
+        with on_device_of(grad_out) as s:
+            _det_call(l, "group_linear_grad_w", l.epnet_group_linear_grad_w_det_workspace_bytes(b, c, npoints, nsample), grad_out,
+                      (b, c, n, npoints, nsample, pg, px, pn, pi, pw), s, "group_linear_grad_w")
+        return 1
     with on_device_of(grad_out) as s:
         _lib.check(_lib.lib().epnet_group_linear_grad_w(b, c, n, npoints, nsample, pg, px, pn, pi, pw, s), "group_linear_grad_w")
     return 1
@@ -460,6 +500,12 @@ def feature_gather_wrapper(b, c, h, w, n_src, n, align_corners, feature_map, xy,
 def feature_gather_grad_wrapper(b, c, h, w, n, align_corners, grad_out, xy, grad_feature_map):
     pg, px, pf = dev_ptr(grad_out, "grad_out", _F), dev_ptr(xy, "xy", _F), dev_ptr(grad_feature_map, "grad_feature_map", _F)
     need(grad_out, b * c * n, "grad_out"); need(xy, b * n * 2, "xy"); need(grad_feature_map, b * c * h * w, "grad_feature_map")
+    if _deterministic():
+        l = _lib.lib()
+        with on_device_of(grad_out) as s:
+            _det_call(l, "feature_gather_grad", l.epnet_feature_gather_grad_det_workspace_bytes(b, h, w, n), grad_out,
+                      (b, c, h, w, n, int(bool(align_corners)), pg, px, pf), s, "feature_gather_grad")
+        return 1
     with on_device_of(grad_out) as s:
         _lib.check(_lib.lib().epnet_feature_gather_grad(b, c, h, w, n, int(bool(align_corners)), pg, px, pf, s), "feature_gather_grad")
     return 1

@@ -21,7 +21,8 @@
  *
  * Arithmetic contract (DESIGN.md "Parity definition"): IEEE fp32, source order, no fused
  * contraction; integer outputs bit-exact versus oracle/ (the CPU restatement of the reference
- * kernels), float copies exact, float sums to 1e-5.
+ * kernels), float copies exact, float sums to 1e-5 -- except the deterministic gradients (*_det,
+ * below), whose scatter-adds are bit-exact versus the oracle's sequential loops.
  */
 #ifndef EPNET_OPS_H
 #define EPNET_OPS_H
@@ -209,6 +210,56 @@ int epnet_feature_gather(int b, int c, int h, int w, int n_src, int n, int align
                          const float *xy, const int *idx, float *out, float *xy_out, epnet_stream_t stream);
 int epnet_feature_gather_grad(int b, int c, int h, int w, int n, int align_corners, const float *grad_out, const float *xy,
                               float *grad_feature_map, epnet_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Deterministic gradients (torch.use_deterministic_algorithms(True) in the Python surface). The default gradient entry
+ * points above add with float atomics, so their bits change from run to run. The *_det forms below give bits that depend
+ * on nothing but the inputs and the shape: not on the stream, concurrent work, epnet_set_tuning, the placement of
+ * workgroups or the batch position of a scene. They use no float atomics, allocate nothing and synchronise nothing (graph
+ * capturable); the scratch is the caller's: workspace (256-byte aligned) of at least the matching *_det_workspace_bytes,
+ * which depends on the shape alone and is 0 only for an empty problem. Same EPNET_ELIMIT limits as the default entry
+ * point; in addition the entries of one scene (npoints * nsample, 3 n, 4 n) must stay below 2^31.
+ *
+ * Scatter-add gradients (gather_points_grad, group_points_grad, group_concat_grad, three_interpolate_grad): grad_points
+ * receives exactly the bits that the oracle's sequential loop (oracle/epnet_oracle.c: oracle_gather_points_grad,
+ * oracle_group_points_grad, oracle_three_interpolate_grad) leaves in the same buffer from the same contents. For each
+ * (scene, channel) the terms are taken in ascending entry order -- for three_interpolate_grad (unknown, then k = 0, 1, 2) --
+ * each term is one fp32 product where there is a weight (grad_out * weight), and each is added to the running value with
+ * one fp32 add, g[j] = g[j] + term, starting from the buffer's incoming value (so accumulating calls, e.g. two scales into
+ * one buffer, equal the oracle called twice). Entries whose index lies outside [0, n) add nothing (outside the bit-exact
+ * claim; the default entry points leave them undefined).
+ *
+ * epnet_feature_gather_grad_det: for each (scene, channel) the points in ascending order, each point's in-bounds taps in
+ * the order nw, ne, sw, se; term = grad_out * tap weight (the weights of epnet_feature_gather); the same sequential fold
+ * from the buffer's contents.
+ *
+ * epnet_group_linear_grad_w_det: a fixed order that depends on the shape alone. The positions q of a scene (p = npoints *
+ * nsample) are cut into tiles of 4096; in a tile, slot i (0..255) sums the terms of positions tile * 4096 + i + 256 k,
+ * k ascending, from 0 (term = grad_out[b,co,q] * (xyz[b,idx] - new_xyz[b,m])[d], one fp32 subtraction and one product);
+ * the 64 slots of each quarter are combined by the butterfly v[i] = v[i] + v[i ^ o], o = 32, 16, 8, 4, 2, 1; the
+ * quarters are added in order from 0; the tiles of a scene in ascending order from 0; the scenes in ascending order from
+ * 0; and the total is added to grad_w once: grad_w = grad_w + total. Values stay within the default's bound against the
+ * oracle.
+ * -------------------------------------------------------------------------------------- */
+size_t epnet_gather_points_grad_det_workspace_bytes(int b, int n, int npoints);
+int epnet_gather_points_grad_det(int b, int c, int n, int npoints, const float *grad_out, const int *idx, float *grad_points,
+                                 void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+size_t epnet_group_points_grad_det_workspace_bytes(int b, int n, int npoints, int nsample);
+int epnet_group_points_grad_det(int b, int c, int n, int npoints, int nsample, const float *grad_out, const int *idx,
+                                float *grad_points, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+size_t epnet_group_concat_grad_det_workspace_bytes(int b, int n, int npoints, int nsample);
+int epnet_group_concat_grad_det(int b, int c, int n, int npoints, int nsample, const float *grad_out, const int *idx,
+                                float *grad_features, int use_xyz, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+size_t epnet_three_interpolate_grad_det_workspace_bytes(int b, int n, int m);
+int epnet_three_interpolate_grad_det(int b, int c, int n, int m, const float *grad_out, const int *idx, const float *weight,
+                                     float *grad_points, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+size_t epnet_feature_gather_grad_det_workspace_bytes(int b, int h, int w, int n);
+int epnet_feature_gather_grad_det(int b, int c, int h, int w, int n, int align_corners, const float *grad_out, const float *xy,
+                                  float *grad_feature_map, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+size_t epnet_group_linear_grad_w_det_workspace_bytes(int b, int c, int npoints, int nsample);
+int epnet_group_linear_grad_w_det(int b, int c, int n, int npoints, int nsample, const float *grad_out, const float *xyz,
+                                  const float *new_xyz, const int *idx, float *grad_w, void *workspace, size_t workspace_bytes,
+                                  epnet_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------
  * scene index: one spatial sort of a level's points (1024 <= n <= 65536), built once in caller scratch and
