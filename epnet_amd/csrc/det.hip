@@ -253,11 +253,11 @@ __global__ __launch_bounds__(kThreads) void sum_kernel(int c, int n, int p, int 
         if (r < nr) g[(size_t)r * n] = acc[r];
 }
 
-// the whole scatter: keys are in s.keys[0] / s.vals[0] already
+// the whole scatter: keys are in s.keys[0] / s.vals[0] already. The caller has checked every limit (b, ceil(c / kRows), p, n)
+// before its key launch, so that a refused shape launches nothing.
 template <int DIV, bool W>
 static int run_scatter(int b, int c, int n, int p, int row, size_t gstride, const float *grad_out, const float *weight,
                        float *grad, char *ws, const Scratch &s, hipStream_t st, const char *what) {
-    if (div_up(c, kRows) > 65535) return EPNET_ELIMIT;
     const int tiles = (int)div_up64(p, kTile);
     const int passes = passes_of(n);
     int cur = 0;
@@ -286,7 +286,7 @@ static int index_scatter(int b, int c, int n, long long p, size_t gstride, const
                          float *grad, void *workspace, size_t workspace_bytes, hipStream_t st, const char *what) {
     if (b == 0 || c == 0 || p == 0 || n == 0) return EPNET_OK;
     if (!(grad_out && idx && grad && (!W || weight))) return EPNET_EINVAL;
-    if (p > 0x7fffffffll || b > 65535) return EPNET_ELIMIT;
+    if (p > 0x7fffffffll || b > 65535 || div_up(c, kRows) > 65535) return EPNET_ELIMIT;
     const Scratch s = scratch_of(b, p, n, false);
     if (!workspace || workspace_bytes < s.total) return EPNET_ENOMEM;
     if ((uintptr_t)workspace & 255) return EPNET_EINVAL;
@@ -460,7 +460,7 @@ extern "C" int epnet_feature_gather_grad_det(int b, int c, int h, int w, int n, 
     if (b == 0 || n == 0 || c == 0) return EPNET_OK;
     EPNET_REQUIRE(grad_out && xy && grad_feature_map && h > 0 && w > 0);
     const long long hw = (long long)h * w, p = (long long)n * 4;
-    if (b > 65535 || hw > 0x7fffffffll || p > 0x7fffffffll) return EPNET_ELIMIT;
+    if (b > 65535 || hw > 0x7fffffffll || p > 0x7fffffffll || div_up(c, det::kRows) > 65535) return EPNET_ELIMIT;
     const det::Scratch s = det::scratch_of(b, p, hw, true);
     if (!workspace || workspace_bytes < s.total) return EPNET_ENOMEM;
     if ((uintptr_t)workspace & 255) return EPNET_EINVAL;

@@ -70,38 +70,42 @@ def feature_gather_grad(start, grad_out, xy, align_corners):
 TILE, THREADS, WAVE = 4096, 256, 64
 
 
-def group_linear_grad_w(start, grad_out, xyz, new_xyz, idx):
+def group_linear_grad_w(start, grad_out, xyz, new_xyz, idx, chunk=256):
     """the fixed order of epnet_group_linear_grad_w_det: per scene, tiles of 4096 positions, slot i of a tile sums positions
     i, i + 256, ... in order from 0; xor butterfly over the 64 slots of each quarter; quarters in order from 0; tiles in
-    order from 0; scenes in order from 0; grad_w = grad_w + total"""
+    order from 0; scenes in order from 0; grad_w = grad_w + total. (Scenes are restated `chunk` at a time, each on its own;
+    the rounds of a lone tile that hold no position would leave every slot as it is and are left out.)"""
     b, c, npoint, ns = grad_out.shape
     p = npoint * ns
+    tiles = -(-p // TILE)
+    rounds = TILE // THREADS if tiles > 1 else -(-p // THREADS)
+    present = np.zeros(tiles * rounds * THREADS, bool)
+    present[:p] = True
+    present = present.reshape(tiles, rounds, THREADS)
     total = np.zeros((c, 3), f32)
-    for bi in range(b):
-        ix = idx[bi].reshape(p).astype(np.int64)
-        d = (xyz[bi][ix] - np.repeat(new_xyz[bi], ns, axis=0)).astype(f32)           # (p, 3)
-        terms = (grad_out[bi].reshape(c, p)[:, :, None] * d[None]).astype(f32)        # (c, p, 3)
-        tiles = -(-p // TILE)
-        pad = np.zeros((c, tiles * TILE, 3), f32)
-        pad[:, :p] = terms
-        present = np.zeros(tiles * TILE, bool)
-        present[:p] = True
-        pad = pad.reshape(c, tiles, TILE // THREADS, THREADS, 3)
-        present = present.reshape(tiles, TILE // THREADS, THREADS)
-        acc = np.zeros((c, tiles, THREADS, 3), f32)
-        for k in range(TILE // THREADS):
-            acc = np.where(present[None, :, k, :, None], (acc + pad[:, :, k]).astype(f32), acc)
-        acc = acc.reshape(c, tiles, THREADS // WAVE, WAVE, 3)
-        lanes = np.arange(WAVE)
+    for b0 in range(0, b, chunk):
+        bs = np.arange(b0, min(b, b0 + chunk))
+        ix = idx[bs].reshape(len(bs), p).astype(np.int64)
+        d = (xyz[bs[:, None], ix] - np.repeat(new_xyz[bs], ns, axis=1)).astype(f32)                  # (k, p, 3)
+        terms = (grad_out[bs].reshape(len(bs), c, p)[:, :, :, None] * d[:, None]).astype(f32)      # (k, c, p, 3)
+        pad = np.zeros((len(bs), c, tiles * rounds * THREADS, 3), f32)
+        pad[:, :, :p] = terms
+        pad = pad.reshape(len(bs), c, tiles, rounds, THREADS, 3)
+        acc = np.zeros((len(bs), c, tiles, THREADS, 3), f32)
+        for k in range(rounds):
+            acc = np.where(present[None, None, :, k, :, None], (acc + pad[:, :, :, k]).astype(f32), acc)
+        acc = acc.reshape(len(bs), c, tiles, THREADS // WAVE, WAVE, 3)
         off = WAVE // 2
-        while off >= 1:
-            acc = (acc + acc[:, :, :, lanes ^ off]).astype(f32)
+        while off >= 1:                 # lane l ^ off: the lanes as (WAVE / 2 off, 2, off), the middle axis reversed
+            part = acc.reshape(acc.shape[:-2] + (WAVE // (2 * off), 2, off, 3))[..., ::-1, :, :].reshape(acc.shape)
+            acc = (acc + part).astype(f32)
             off //= 2
-        v = np.zeros((c, tiles, 3), f32)
+        v = np.zeros((len(bs), c, tiles, 3), f32)
         for wv in range(THREADS // WAVE):
-            v = (v + acc[:, :, wv, 0]).astype(f32)
-        scene = np.zeros((c, 3), f32)
+            v = (v + acc[:, :, :, wv, 0]).astype(f32)
+        scene = np.zeros((len(bs), c, 3), f32)
         for t in range(tiles):
-            scene = (scene + v[:, t]).astype(f32)
-        total = (total + scene).astype(f32)
+            scene = (scene + v[:, :, t]).astype(f32)
+        for k in range(len(bs)):
+            total = (total + scene[k]).astype(f32)
     return (np.asarray(start, f32) + total).astype(f32)

@@ -73,6 +73,41 @@ def test_det_entry_points_validate_without_a_gpu(hiplib):
     assert l.epnet_group_linear_grad_w_det(1, 4, 16, 4, 4, 256, 256, 256, 256, 256, 256, 0, None) == -3
 
 
+@pytest.mark.skipif(torch.cuda.is_available(), reason="hands the library placeholder pointers: only where no GPU could run them")
+def test_every_det_limit_is_refused_before_a_launch(hiplib):
+    """each EPNET_ELIMIT condition of each *_det entry point returns -4 with placeholder pointers and a workspace that passes every
+    other check. Without a GPU a launch fails (-2, the first assertion), so -4 also shows that nothing was launched first"""
+    l = hiplib
+    P, WS = 256, 1 << 40                   # placeholder pointer (256-byte aligned), workspace size that is never short
+    big_b, big_c = 65536, 8 * 65535 + 1    # b > 65535; ceil(c / 8) = 65536 fold rows / grad_w chunks
+    calls = {
+        "gather_points_grad": lambda b, c, n, m: l.epnet_gather_points_grad_det(b, c, n, m, P, P, P, P, WS, None),
+        "group_points_grad": lambda b, c, n, m, ns=1: l.epnet_group_points_grad_det(b, c, n, m, ns, P, P, P, P, WS, None),
+        "group_concat_grad": lambda b, c, n, m, ns=1: l.epnet_group_concat_grad_det(b, c, n, m, ns, P, P, P, 1, P, WS, None),
+        "three_interpolate_grad": lambda b, c, n, m: l.epnet_three_interpolate_grad_det(b, c, n, m, P, P, P, P, P, WS, None),
+        "feature_gather_grad": lambda b, c, h, w, n: l.epnet_feature_gather_grad_det(b, c, h, w, n, 1, P, P, P, P, WS, None),
+        "group_linear_grad_w": lambda b, c, n, m, ns=1: l.epnet_group_linear_grad_w_det(b, c, n, m, ns, P, P, P, P, P, P, WS, None),
+    }
+    assert calls["group_points_grad"](1, 4, 16, 4, 4) == -2          # a shape inside the limits reaches its first launch
+    refused = {
+        "gather_points_grad": [(big_b, 1, 16, 4), (1, big_c, 16, 4)],
+        "group_points_grad": [(big_b, 1, 16, 4), (1, big_c, 16, 4), (1, 1, 16, 65536, 32768)],
+        "group_concat_grad": [(big_b, 1, 16, 4), (1, big_c, 16, 4), (1, 1, 16, 65536, 32768)],
+        # 3 n entries: n = 715827883 -> 2^31 + 1
+        "three_interpolate_grad": [(big_b, 1, 16, 4), (1, big_c, 16, 4), (1, 1, 715827883, 16)],
+        # 4 n entries: n = 2^29 -> 2^31; h w = 65536 * 32768 = 2^31
+        "feature_gather_grad": [(big_b, 1, 4, 4, 4), (1, big_c, 4, 4, 4), (1, 1, 4, 4, 1 << 29), (1, 1, 65536, 32768, 4)],
+        "group_linear_grad_w": [(big_b, 1, 16, 4), (1, big_c, 16, 4), (1, 1, 16, 65536, 32768)],
+    }
+    assert set(refused) == set(DET_OPS)
+    for op, shapes in refused.items():
+        for shape in shapes:
+            assert calls[op](*shape) == -4, (op, shape)
+        # (the same calls one step inside the b and c limits get past the limit check)
+        assert calls[op](*((65535,) + shapes[0][1:])) != -4, op
+        assert calls[op](*((1, 8 * 65535) + shapes[1][2:])) != -4, op
+
+
 # ---- the Python surface, against a recording stand-in for the library ----------------------------------------------------------
 # torch.use_deterministic_algorithms is process-wide: the flag is switched on only in a child process (tests/det_dispatch_probe.py),
 # so that nothing of it -- the flag, its NaN-filled allocations, the stand-in library -- reaches the other tests of this process.
@@ -186,3 +221,30 @@ def test_group_linear_order_restatement_is_the_sum():
     exact = start + np.einsum("bcp,bpk->ck", go.reshape(b, c, -1).astype(np.float64), d)
     assert np.allclose(got, exact, rtol=1e-5, atol=1e-4)
     same_bits(got, R.group_linear_grad_w(start, go, xyz, new_xyz, idx))
+
+
+# ---- the GPU sweep's generator (tests/test_deterministic_sweep.py) ---------------------------------------------------------------
+def test_det_sweep_keeps_every_boundary():
+    """for every op, the seeded case list has a case on either side of each radix pass-count boundary and of the 4096-entry sort
+    tile, so that an edit of the generator cannot drop that coverage unnoticed"""
+    import test_deterministic_sweep as S
+    assert set(S.OPS) == set(DET_OPS)
+    assert [S.passes_of(n) for n in (1, 2, 256, 257, 65536, 65537, 1 << 24, (1 << 24) + 1)] == [0, 1, 1, 2, 2, 3, 3, 4]
+    assert [cs["i"] for cs in S.CASES] == list(range(len(S.CASES)))
+    for op in DET_OPS:
+        cases = [cs for cs in S.CASES if cs["op"] == op]
+        ns = {cs["n"] for cs in cases}
+        for lo, hi in S.PASS_BOUNDARIES:
+            assert lo in ns and hi in ns, (op, lo, hi)
+        assert {S.passes_of(n) for n in ns} >= {0, 1, 2, 3, 4}, op
+        assert any(S.TILE - 4 <= cs["p"] <= S.TILE for cs in cases), op             # one full tile (3 n, 4 n: the nearest count)
+        assert any(S.TILE < cs["p"] <= S.TILE + 4 for cs in cases), op              # ... and one entry past it
+        assert any(cs["p"] >= 10 ** 6 for cs in cases) or op == "group_linear_grad_w", op
+        assert {1, 7, 8, 9, 17} <= {cs["c"] for cs in cases} and max(cs["c"] for cs in cases) >= 256, op
+        assert {1, 2, 3, 17} <= {cs["b"] for cs in cases} and {255, 256, 257} <= {cs["b"] for cs in cases}, op
+        fams = {cs["family"] for cs in cases}
+        assert fams >= set(S.FAMILIES) - ({"out_of_range"} if op == "group_linear_grad_w" else set()), (op, fams)
+        for cs in cases:
+            assert cs["p"] == cs["npts"] * {"three_interpolate_grad": 3, "feature_gather_grad": 4}.get(op, cs["ns"]), cs
+        if op in ("group_concat_grad", "feature_gather_grad"):
+            assert {cs["flag"] for cs in cases} == {True, False}, op

@@ -470,3 +470,169 @@ def test_scene_count_limit(oracle, outputs, name):
     torch.cuda.synchronize()
     for t in outs:
         assert bool((t == 7.25).all()), (name, "an output was written past the limit")
+
+
+# ---- the deterministic gradients (include/epnet_ops.h "*_det") at the bench's batch, past 2^31 and at the scene-count limit ----------
+def _det_oracle():
+    from oracle import oracle
+    oracle.build()
+    oracle.lib()
+    return oracle
+
+
+# (op, n targets, npoints / unknowns, nsample, channels): config 2's level 1 (16384 -> 4096 x 16 / 32) and level 2 (4096 -> 1024 x 32)
+# groupings and its last FP module (16384 unknowns, 4096 known). Level 1 groups coordinates only in the bench, and the FP module's
+# 256 channels would pass 4 GB of host copies: 17 / 9 / 65 channels there (>= 9 and no multiple of 8: partial fold rows)
+_DET_BATCH = (("group_points_grad", 16384, 4096, 16, 17), ("group_points_grad", 16384, 4096, 32, 9),
+              ("group_concat_grad", 16384, 4096, 16, 17), ("group_concat_grad", 16384, 4096, 32, 9),
+              ("group_points_grad", 4096, 1024, 32, 96), ("group_concat_grad", 4096, 1024, 32, 96),
+              ("three_interpolate_grad", 4096, 16384, 3, 65))
+
+
+@pytest.mark.parametrize("op,n,m,ns,c", _DET_BATCH, ids=["%s_n%d_m%d_ns%d_c%d" % k for k in _DET_BATCH])
+def test_det_gradients_at_the_benchs_batch(outputs, op, n, m, ns, c):
+    """the deterministic gradients of config 2's shapes at B = 256 from a nonzero buffer, every scene bit for bit the oracle's loop"""
+    from epnet_amd import pointnet2_cuda as ext
+    from test_deterministic_gpu import deterministic, oracle_group_grad, oracle_interp_grad, same_bits
+    o = _det_oracle()
+    b = BATCH
+    g = torch.Generator(device=DEV).manual_seed(m + ns + c)
+    ch0 = 3 if op == "group_concat_grad" else 0
+    start = torch.randn((b, c, n), generator=g, device=DEV)
+    grad = out_tensor(outputs, (b, c, n))
+    grad.copy_(start)
+    if op == "three_interpolate_grad":
+        idx = torch.randint(0, n, (b, m, 3), generator=g, device=DEV, dtype=torch.int32)
+        w = torch.rand((b, m, 3), generator=g, device=DEV)
+        w = (w / w.sum(-1, keepdim=True)).contiguous()
+        go = torch.randn((b, c, m), generator=g, device=DEV)
+        with deterministic():
+            ext.three_interpolate_grad_wrapper(b, c, m, n, go, idx, w, grad)
+    else:
+        idx = torch.randint(0, n, (b, m, ns), generator=g, device=DEV, dtype=torch.int32)
+        idx[:, :, ns // 2:] = idx[:, :, :1]                      # ball-query padding: the first hit repeated
+        go = torch.randn((b, ch0 + c, m, ns), generator=g, device=DEV)
+        with deterministic():
+            if op == "group_points_grad":
+                ext.group_points_grad_wrapper(b, c, n, m, ns, go, idx, grad)
+            else:
+                ext.group_concat_grad_wrapper(b, c, n, m, ns, go, idx, grad, True)
+    torch.cuda.synchronize()
+    got, s_h, go_h, idx_h = host(grad), host(start), host(go), host(idx)
+    w_h = host(w) if op == "three_interpolate_grad" else None
+    del go, start
+
+    def scene(s):
+        sl = slice(s, s + 1)
+        if op == "three_interpolate_grad":
+            want = oracle_interp_grad(o, s_h[sl], go_h[sl], idx_h[sl], w_h[sl])
+        else:
+            want = oracle_group_grad(o, s_h[sl], go_h[sl, ch0:], idx_h[sl])
+        try:
+            same_bits(got[sl], want)
+        except AssertionError:
+            return s
+        return None
+    with ThreadPoolExecutor(max_workers=WORKERS) as pool:
+        bad = [s for s in pool.map(scene, range(b)) if s is not None]
+    assert not bad, "%s at B = %d: %d scenes differ from the oracle's loop: %s" % (op, b, len(bad), bad)
+
+
+def test_group_points_grad_det_past_2_to_the_31_elements(outputs):
+    """the deterministic group_points_grad from the (33, 64, 16384, 64) grad_out of test_group_points_output_past_2_to_the_31_elements
+    (2.2e9 elements): every scene against a float64 index_add_ on the device, the straddling scenes and both ends bit for bit"""
+    from epnet_amd import pointnet2_cuda as ext
+    from test_deterministic_gpu import deterministic, oracle_group_grad, same_bits
+    o = _det_oracle()
+    b, c, n, m, ns = 33, 64, 65536, 16384, 64
+    p = m * ns
+    assert b * c * p > 1 << 31
+    g = torch.Generator(device=DEV).manual_seed(32)
+    idx = torch.randint(0, n, (b, m, ns), generator=g, device=DEV, dtype=torch.int32)
+    grad_out = torch.randn((b, c, m, ns), generator=g, device=DEV)
+    start = torch.randn((b, c, n), generator=g, device=DEV)
+    grad = out_tensor(outputs, (b, c, n))
+    grad.copy_(start)
+    with deterministic():
+        ext.group_points_grad_wrapper(b, c, n, m, ns, grad_out, idx, grad)
+    bad = []
+    for s in range(b):
+        flat = idx[s].reshape(p).long()
+        terms = grad_out[s].reshape(c, p).double()
+        want = start[s].double().index_add_(1, flat, terms)
+        mag = start[s].double().abs().index_add_(1, flat, terms.abs())
+        del terms
+        err = (grad[s].double() - want).abs()
+        if not bool((err <= 2e-7 * mag + 1e-5 * want.abs().clamp(min=1.0)).all()):      # test_gpu_sweep.assert_scatter_sum's bound
+            bad.append((s, float(err.max())))
+    assert not bad, ("group_points_grad (deterministic) vs float64 index_add_, (scene, max error)", bad)
+    for s in sorted(straddling_scenes((b, c, m, ns), 4) | {0, b - 1}):
+        sl = slice(s, s + 1)
+        same_bits(host(grad[sl]), oracle_group_grad(o, host(start[sl]), host(grad_out[sl]), host(idx[sl])))
+
+
+def _det_lim_case(name, b, g, x, o):
+    """(call, outputs, check(scene)) of one deterministic gradient at batch b, from a nonzero buffer; the check is the contract,
+    bit for bit (group_linear_grad_w: its sum over all scenes, once)"""
+    import det_restate as R
+    from epnet_amd import pointnet2_cuda as ext
+    from test_deterministic_gpu import oracle_gather_grad, oracle_group_grad, oracle_interp_grad, same_bits
+    n, c, m, ns = _LIM_N, _LIM_C, _LIM_M, _LIM_NS
+    d = {k: dev(v) for k, v in x.items()}
+    sl = lambda a, s: a[s:s + 1]                           # noqa: E731
+    starts = {"group_linear_grad_w": x["wx"], "three_interpolate_grad": x["gm"], "feature_gather_grad": x["fmap"]}
+    start = starts.get(name, x["feats"])
+    out = out_tensor(g, start.shape)
+    out.copy_(torch.from_numpy(start))
+
+    def bits(want):
+        return lambda s: same_bits(host(sl(out, s)), want(s))
+    if name == "group_points_grad":
+        go = d["go"][:, 3:].contiguous()
+        return (lambda: ext.group_points_grad_wrapper(b, c, n, m, ns, go, d["idx"], out), [out],
+                bits(lambda s: oracle_group_grad(o, sl(start, s), sl(x["go"], s)[:, 3:], sl(x["idx"], s))))
+    if name == "group_concat_grad":
+        return (lambda: ext.group_concat_grad_wrapper(b, c, n, m, ns, d["go"], d["idx"], out, True), [out],
+                bits(lambda s: oracle_group_grad(o, sl(start, s), sl(x["go"], s)[:, 3:], sl(x["idx"], s))))
+    if name == "gather_points_grad":
+        return (lambda: ext.gather_points_grad_wrapper(b, c, n, m, d["gm"], d["gi"], out), [out],
+                bits(lambda s: oracle_gather_grad(o, sl(start, s), sl(x["gm"], s), sl(x["gi"], s))))
+    if name == "three_interpolate_grad":
+        return (lambda: ext.three_interpolate_grad_wrapper(b, c, n, m, d["gn"], d["nn"], d["w"], out), [out],
+                bits(lambda s: oracle_interp_grad(o, sl(start, s), sl(x["gn"], s), sl(x["nn"], s), sl(x["w"], s))))
+    if name == "feature_gather_grad":
+        return (lambda: ext.feature_gather_grad_wrapper(b, c, 3, 5, n, True, d["gn"], d["xy"], out), [out],
+                bits(lambda s: R.feature_gather_grad(sl(start, s), sl(x["gn"], s), sl(x["xy"], s), True)))
+    if name == "group_linear_grad_w":
+        go = d["go"][:, 3:].contiguous()
+
+        def check(s):
+            if s == 0:
+                same_bits(host(out), R.group_linear_grad_w(start, np.ascontiguousarray(x["go"][:, 3:]), x["xyz"], x["new_xyz"], x["idx"]))
+        return lambda: ext.group_linear_grad_w_wrapper(b, c, n, m, ns, go, d["xyz"], d["new_xyz"], d["idx"], out), [out], check
+    raise ValueError(name)
+
+
+@pytest.mark.parametrize("name", ("gather_points_grad", "group_points_grad", "group_concat_grad", "three_interpolate_grad",
+                                  "feature_gather_grad", "group_linear_grad_w"))
+def test_scene_count_limit_det(outputs, name):
+    """test_scene_count_limit under torch.use_deterministic_algorithms(True): b = 65535 runs its *_det entry point, scenes 0, 32767
+    and 65534 are the contract's bits; b = 65536 raises a RuntimeError that names the op and leaves the output as it was"""
+    from test_deterministic_gpu import deterministic
+    o = _det_oracle()
+    lim = 65535
+    x = _lim_inputs(lim + 1)
+    call, outs, check = _det_lim_case(name, lim, outputs, {k: v[:lim] if v.ndim > 1 and v.shape[0] == lim + 1 else v for k, v in x.items()}, o)
+    with deterministic():
+        call()
+    torch.cuda.synchronize()
+    for s in (0, lim // 2, lim - 1):
+        check(s)
+    call, outs, _ = _det_lim_case(name, lim + 1, outputs, x, o)
+    for t in outs:
+        t.fill_(7.25)
+    with deterministic(), pytest.raises(RuntimeError, match=name):
+        call()
+    torch.cuda.synchronize()
+    for t in outs:
+        assert bool((t == 7.25).all()), (name, "an output was written past the limit")
