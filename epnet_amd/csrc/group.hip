@@ -182,6 +182,7 @@ __global__ __launch_bounds__(kGLdsThreads) void gather_rows_lds_kernel(int c, in
 #ifndef EPNET_GATHER_LDS2_UNROLL
 #define EPNET_GATHER_LDS2_UNROLL 1   // see EPNET_GATHER_LDS_UNROLL
 #endif
+constexpr long long kGatherLds2MinPositions = 3 * kGLdsThreads * 4;  // both scales together, see epnet_group_concat_multi
 // the same for the TWO scales of an MSG level at once: both gather from the same feature rows, so the rows are
 // staged once and then serve both index sets (saves one 64 KB staging pass per workgroup: 7-12 % of the traffic)
 template <bool QUAD>
@@ -768,14 +769,20 @@ extern "C" int epnet_group_concat_multi(int b, int c, int n, int npoints, int ns
     if (fused) {
         rows = kLdsBudget / (n * 4);
         if (rows > c) rows = c;
-        if (rows > 32) rows = 32;
+        if (rows > 32) rows = 32;  // (64 rows at n = 256: the last level 0.286 against 0.277 ms beside the sampling)
         quad = (c & 3) == 0 && (n & 3) == 0 && rows >= 4 && ((uintptr_t)features & 15) == 0;
         if (quad) rows &= ~3;
+        long long p_both = 0;
         for (int k = 0; k < 2 && fused; ++k) {
             const long long p = (long long)npoints * nsamples[k];
-            fused = p >= 2048 && p <= 0x7fffffffll && p % 4 == 0 && idx[k] && out[k] &&
+            fused = p > 0 && p <= 0x7fffffffll && p % 4 == 0 && idx[k] && out[k] &&
                     (((uintptr_t)idx[k] | (uintptr_t)out[k]) % 16 == 0) && ((size_t)(ch0 + c) * (size_t)p) % 4 == 0;
+            p_both += p;
         }
+        // a workgroup stages its rows ONCE for both scales, so what has to amortise the staging is the positions of the two
+        // together: three passes of the workgroup (256 threads x 4 positions), the last SA level's 64 x (16 + 32). Asking
+        // 2048 of EACH scale sent that level to two launches, its 1024-position scale to the few-channel kernel.
+        fused = fused && p_both >= kGatherLds2MinPositions;
         fused = fused && (long long)b * div_up(c, rows) >= 512;  // one workgroup serves ALL positions: needs a full chip
     }
     if (!fused) {
