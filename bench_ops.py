@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
     args = ap.parse_args()
     import torch
     from epnet_amd import iou3d_cuda, iou3d_utils, kitti_utils, pointnet2_cuda as p2, roipool3d_cuda, synth
@@ -46,7 +47,88 @@ def main():
         print(json.dumps({"op": op, "shape": shape, "ms": round(ms, 4), "algorithmic_bytes": nbytes,
                           "GBps": round(nbytes / (ms * 1e-3) / 1e9, 2), "note": note}), flush=True)
 
+    def timeit_pair(fa, fb):
+        """medians of two alternatives measured ALTERNATELY inside one call (same clocks, same cache state), warm-up first"""
+        for _ in range(3):
+            fa(); fb()
+        torch.cuda.synchronize()
+        ta, tb = [], []
+        for _ in range(args.reps):
+            for fn, ts in ((fa, ta), (fb, tb)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+        return sorted(ta)[len(ta) // 2], sorted(tb)[len(tb) // 2]
+
     g = torch.Generator().manual_seed(0)
+
+    def stage2_infer():
+        """second-stage inference: each fused op against the composition from the ops the package had before it -- the
+        reference's own statements (lib/net/rcnn_net.py:152-162, tools/eval_rcnn.py:663-683) on this package's surface"""
+        from epnet_amd import roipool3d_utils
+        n, m, s, c = 16384, 100, 512, 130
+        for bsz in (1, 2, 16):
+            pts = synth.scenes("kitti", bsz, n, seed=5).to(dev)
+            feat = torch.randn((bsz, n, c), generator=g).to(dev)
+            rois = torch.stack([synth.proposal_boxes(m, seed=50 + i)[0] for i in range(bsz)]).to(dev)
+
+            def composed():
+                pooled, flag = roipool3d_utils.roipool3d_gpu(pts, feat, rois, 0.2, sampled_pt_num=s)
+                pooled[:, :, :, 0:3] -= rois[:, :, 0:3].unsqueeze(dim=2)
+                for k in range(bsz):
+                    pooled[k, :, :, 0:3] = kitti_utils.rotate_pc_along_y_torch(pooled[k, :, :, 0:3], rois[k, :, 6])
+                return pooled, flag
+
+            def fused():
+                return roipool3d_utils.roipool3d_canonical_gpu(pts, feat, rois, 0.2, sampled_pt_num=s)
+            (pc, fc), (pf, ff) = composed(), fused()
+            close = bool(torch.equal(fc, ff) and torch.equal(pc[..., 3:][fc == 0], pf[..., 3:][ff == 0])
+                         and torch.allclose(pc[..., 0:3], pf[..., 0:3], rtol=0, atol=1e-4))
+            ms_c, ms_f = timeit_pair(composed, fused)
+            report("roipool3d_canonical", {"B": bsz, "N": n, "M": m, "S": s, "C": c}, ms_f,
+                   bsz * (n * 12 + n * c * 4 + m * 28 + m * s * (3 + c) * 4 + m * 4),
+                   "one launch, no zero-fill; composition (roipool3d_gpu + centre subtraction + per-scene rotation loop): %.4f ms; "
+                   "same flags and features, xyz within 1e-4: %s; empty boxes: %d" % (ms_c, close, int(ff.sum())))
+        for m in (100, 512):
+            for bsz in (1, 2, 16):
+                boxes = torch.stack([synth.proposal_boxes(m, seed=70 + i, num_objects=12)[0] for i in range(bsz)]).to(dev)
+                raw = (torch.randn((bsz, m), generator=g) * 2).to(dev)
+                norm = torch.sigmoid(raw)
+                det_b = torch.empty((bsz, m, 7), device=dev)
+                det_s = torch.empty((bsz, m), device=dev)
+                det_c = torch.empty((bsz,), dtype=i32, device=dev)
+
+                def composed():
+                    inds = norm > 0.2
+                    out = []
+                    for k in range(bsz):
+                        cur_inds = inds[k].view(-1)
+                        if cur_inds.sum() == 0:
+                            continue
+                        sel_b, sel_s = boxes[k, cur_inds], raw[k, cur_inds]
+                        keep_idx = iou3d_utils.nms_gpu(kitti_utils.boxes3d_to_bev_torch(sel_b), sel_s, 0.1).view(-1)
+                        out.append((sel_b[keep_idx].cpu(), sel_s[keep_idx].cpu()))
+                    return out
+
+                def fused():
+                    iou3d_cuda.rcnn_detections_gpu(boxes, raw, norm, 0.2, 0.1, det_b, det_s, det_c)
+
+                def fused_read_back():
+                    fused()
+                    return det_b.cpu(), det_s.cpu(), det_c.cpu()
+                want = composed()
+                got_b, got_s, got_c = fused_read_back()
+                same = got_c.tolist() == [w[1].numel() for w in want] and all(
+                    torch.equal(got_b[k, :w[1].numel()], w[0]) and torch.equal(got_s[k, :w[1].numel()], w[1]) for k, w in enumerate(want))
+                ms_c, ms_f = timeit_pair(composed, fused)
+                ms_r = timeit(fused_read_back)
+                report("rcnn_detections", {"B": bsz, "M": m, "score_thresh": 0.2, "nms_thresh": 0.1, "kept": got_c.tolist()}, ms_f,
+                       bsz * (m * 28 + m * 8 + m * 32 + 4),
+                       "select + batched rotated NMS + emit, no host sync; with one read-back of the three results: %.4f ms; composition "
+                       "(per-scene loop over nms_gpu with its read-backs): %.4f ms; same result: %s" % (ms_r, ms_c, same))
+
+    if args.stage2_only:
+        return stage2_infer()
     # ---- NMS at the proposal-layer sizes (RPN.NMS_TYPE normal, N <= 6300 / 2700, thresh 0.85) and eval rotated NMS
     for n, rot, thr in ((6300, False, 0.85), (2700, False, 0.85), (6300, True, 0.8), (512, True, 0.1), (100, True, 0.1)):
         boxes, scores = synth.proposal_boxes(n, seed=n, num_objects=40, jitter=1.5)
@@ -238,6 +320,7 @@ def main():
         gx = torch.empty((bsz, 3, m, ns), device=dev)
         ms = timeit(lambda: p2.group_concat_wrapper(bsz, 0, n, m, ns, xyz, new_xyz, None, bq, gx, True))
         report("group_concat", {"B": bsz, "C": 0, "N": n, "M": m, "ns": ns}, ms, bsz * (m * ns * 4 + 3 * n * 4 + 3 * m * ns * 4))
+    stage2_infer()
 
 
 if __name__ == "__main__":

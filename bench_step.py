@@ -5,6 +5,7 @@
     python bench_step.py --image --rpn-only [--batch 2]       # config 3: two-stream RPN (point + image stream, LI-Fusion) fwd+bwd
     python bench_step.py --image [--gpus N]                   # config 4: the whole rcnn_online step, 62.7 MB of gradients
     python bench_step.py                                      # the point stream alone (round-1 figure)
+    python bench_step.py --infer [--two-stage]                # inference latency: the RPN stage [and the whole detector]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench_step.py --gpus N   # scene-parallel, RCCL
 
 What is timed (forward + backward + SGD step, `--batch` scenes per GPU):
@@ -136,16 +137,20 @@ def synthetic_batch(batch, points, seed, device):
 
 
 def infer(args, model, proposal_layer, xyz):
-    """RPN-stage inference latency: eager launches against one HIP-graph replay"""
+    """inference latency, eager launches against one HIP-graph replay: the RPN stage and, with --two-stage, the whole detector"""
     import torch
     model.eval()
 
+    def rpn():
+        _, feats = model.backbone(xyz)
+        cls = model.rpn_cls(feats).transpose(1, 2).contiguous()
+        reg = model.rpn_reg(feats).transpose(1, 2).contiguous()
+        return feats, cls[:, :, 0].contiguous(), reg
+
     def stage():
         with torch.no_grad():
-            _, feats = model.backbone(xyz)
-            cls = model.rpn_cls(feats).transpose(1, 2).contiguous()
-            reg = model.rpn_reg(feats).transpose(1, 2).contiguous()
-            return proposal_layer(cls[:, :, 0].contiguous(), reg, xyz)
+            _, scores, reg = rpn()
+            return proposal_layer(scores, reg, xyz)
 
     def timed(fn, reps):
         torch.cuda.synchronize()
@@ -154,23 +159,58 @@ def infer(args, model, proposal_layer, xyz):
             fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / reps * 1e3
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(max(3, args.warmup)):
-            eager_out = stage()
-    torch.cuda.current_stream().wait_stream(side)
-    ms_eager = timed(stage, args.steps)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        graph_out = stage()
-    graph.replay()
-    torch.cuda.synchronize()
-    same = all(torch.equal(a, b) for a, b in zip(eager_out, graph_out))
-    ms_graph = timed(graph.replay, args.steps)
+
+    def eager_and_graph(fn):
+        """-> ms eager, ms per replay, graph == eager, the graph's output tensors"""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(3, args.warmup)):
+                eager_out = fn()
+        torch.cuda.current_stream().wait_stream(side)
+        ms_eager = timed(fn, args.steps)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            graph_out = fn()
+        graph.replay()
+        torch.cuda.synchronize()
+        same = all(torch.equal(a, b) for a, b in zip(eager_out, graph_out))
+        return ms_eager, timed(graph.replay, args.steps), same, graph_out
+
+    ms_eager, ms_graph, same, _ = eager_and_graph(stage)
     print(json.dumps({"metric": "RPN-stage inference latency (backbone + heads + proposal layer, eval mode)", "scenes": args.batch,
                       "points_per_scene": args.points, "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3),
-                      "graph_equals_eager": bool(same), "dtype": "f32", "data": "synthetic"}))
+                      "graph_equals_eager": bool(same), "dtype": "f32", "data": "synthetic"}), flush=True)
+    if not args.two_stage:
+        return
+    # the whole detector (lib/net/point_rcnn.py:33-47 + the eval branch of lib/net/rcnn_net.py:138-164 + tools/eval_rcnn.py:555-583,
+    # 663-683): the TEST proposal layer (100 ROIs per scene), canonical ROI pooling, the RCNN stage, decoding + threshold + NMS
+    from epnet_amd import detection_layer as dl, proposal_layer as pl
+    test_layer = pl.ProposalLayer("TEST", cfg=proposal_layer.cfg).to(xyz.device)
+    det_layer = dl.DetectionLayer(dl.default_cfg()).to(xyz.device)
+    # the RCNN heads are length-1 convolutions over 100 ROIs per scene: the dense library's default choice for that shape
+    # accumulates in an order that changes from run to run (last bits), so two EAGER runs already differ; its deterministic
+    # algorithms are asked for here, for the graph == eager comparison to mean something
+    torch.backends.cudnn.deterministic = True
+
+    def detector():
+        with torch.no_grad():
+            feats, scores, reg = rpn()
+            rois, _ = test_layer(scores, reg, xyz)
+            seg_mask = (torch.sigmoid(scores) > 0.3).float()
+            depth = torch.norm(xyz, p=2, dim=2)
+            pts_input, _ = dl.pool_rois(xyz, feats.permute(0, 2, 1).contiguous(), rois, seg_mask, pts_depth=depth, cfg=det_layer.cfg)
+            rcnn_cls, rcnn_reg = model.rcnn(pts_input[..., 0:3], pts_input[..., 3:])
+            rcnn_cls = rcnn_cls.transpose(1, 2).contiguous().squeeze(dim=1)      # (B*M, 1), lib/net/rcnn_net.py:190
+            rcnn_reg = rcnn_reg.transpose(1, 2).contiguous().squeeze(dim=1)      # (B*M, 46)
+            return det_layer(rois, rcnn_cls, rcnn_reg)
+
+    ms_eager, ms_graph, same, out = eager_and_graph(detector)
+    counts = out[5].tolist()                                                     # of the last replay, read after the timed loop
+    print(json.dumps({"metric": "two-stage inference latency (RPN stage + ROI pooling + RCNN stage + detections, eval mode)",
+                      "scenes": args.batch, "points_per_scene": args.points, "rois_per_scene": int(out[0].shape[1]),
+                      "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3), "graph_equals_eager": bool(same),
+                      "detections": counts, "dense_layers_deterministic": True, "dtype": "f32", "data": "synthetic"}), flush=True)
 
 
 def main():
@@ -182,6 +222,9 @@ def main():
     ap.add_argument("--infer", action="store_true",
                     help="instead of the training step: inference latency of the RPN stage (backbone, heads, proposal layer) in "
                          "eval mode, eagerly and replayed from a HIP graph (nothing in the stage synchronises with the host)")
+    ap.add_argument("--two-stage", action="store_true",
+                    help="with --infer: after the RPN-stage line, the whole detector -- TEST proposal layer (100 ROIs per scene), "
+                         "canonical ROI pooling, RCNN stage, decoding + score threshold + rotated NMS -- eagerly and as ONE HIP graph")
     ap.add_argument("--image", action="store_true",
                     help="two-stream backbone: (B,3,384,1280) image ~N(0,1), pixel coordinates ~U[0,1280)xU[0,384), LI-Fusion with "
                          "image attention (BASELINE configs 3 and 4; 15.7 M parameters = 62.7 MB of gradients)")
@@ -194,6 +237,8 @@ def main():
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow EPNET_BENCH_DEVICE / EPNET_BENCH_BACKEND (all ranks on one device, gloo): see bench.py")
     args = ap.parse_args()
+    if args.two_stage and not args.infer:
+        ap.error("--two-stage belongs to --infer")
     if args.infer and args.image:
         ap.error("--infer times the point-stream RPN stage; the two-stream backbone (--image) is timed by the training step only")
     from epnet_amd import scene_shard

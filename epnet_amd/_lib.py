@@ -83,11 +83,14 @@ SIGNATURES = {
     "epnet_aug_roi_by_noise": (_i, [_i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_rpn_proposals_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "epnet_rpn_proposals": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "epnet_rcnn_detections_workspace_bytes": (_sz, [_i, _i]),
+    "epnet_rcnn_detections": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
     "epnet_nms_workspace_bytes": (_sz, [_i]),
     "epnet_nms": (_i, [_vp, _i, _f, _vp, _sz, _vp, _vp, _vp]),
     "epnet_nms_normal": (_i, [_vp, _i, _f, _vp, _sz, _vp, _vp, _vp]),
     "epnet_roipool3d_workspace_bytes": (_sz, [_i, _i, _i]),
     "epnet_roipool3d": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "epnet_roipool3d_canonical": (_i, [_i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_pts_in_boxes3d_host": (_i, [_vp, _vp, _vp, _i64, _i64]),
     "epnet_roipool3d_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64]),
 }

@@ -104,6 +104,25 @@ def rpn_proposals_gpu(proposals, scores, order, distance_based, pre_nms_top_n, p
     return 1
 
 
+@writes("det_boxes3d", "det_scores", "det_count")
+def rcnn_detections_gpu(boxes3d, raw_scores, norm_scores, score_thresh, nms_thresh, det_boxes3d, det_scores, det_count):
+    """tools/eval_rcnn.py:663-683 for the whole batch, no host sync: boxes3d (B,M,7), raw_scores / norm_scores (B,M) ->
+    det_boxes3d (B,M,7), det_scores (B,M) (the kept boxes and their raw scores, zero rows behind), det_count (B) int32
+    (not in the reference extension; see epnet_ops.h)"""
+    b, m = raw_scores.size(0), raw_scores.size(1)
+    pb, pr, pn = dev_ptr(boxes3d, "boxes3d", _F), dev_ptr(raw_scores, "raw_scores", _F), dev_ptr(norm_scores, "norm_scores", _F)
+    ob, os_, oc = dev_ptr(det_boxes3d, "det_boxes3d", _F), dev_ptr(det_scores, "det_scores", _F), dev_ptr(det_count, "det_count", torch.int32)
+    need(boxes3d, b * m * 7, "boxes3d"); need(norm_scores, b * m, "norm_scores")
+    need(det_boxes3d, b * m * 7, "det_boxes3d"); need(det_scores, b * m, "det_scores"); need(det_count, b, "det_count")
+    l = _lib.lib()
+    ws_bytes = l.epnet_rcnn_detections_workspace_bytes(b, m)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=raw_scores.device)
+    with on_device_of(raw_scores) as s:
+        _lib.check(l.epnet_rcnn_detections(b, m, pb, pr, pn, float(score_thresh), float(nms_thresh), ws.data_ptr(), ws.numel(),
+                                           ob, os_, oc, s), "rcnn_detections")
+    return 1
+
+
 def _nms_device(fn_name, boxes, thresh):
     """returns (keep_dev int64 (N,), num_keep_dev int32 (1,)), both on the boxes' device, no sync"""
     pb = dev_ptr(boxes, "boxes", _F)

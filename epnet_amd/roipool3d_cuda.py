@@ -21,6 +21,22 @@ def forward(xyz, boxes3d, pts_feature, pooled_features, pooled_empty_flag):
     return 1
 
 
+@writes("pooled_features", "pooled_empty_flag")
+def forward_canonical(xyz, rois, pts_feature, pool_extra_width, pooled_features, pooled_empty_flag):
+    """roipool3d_gpu on the ROIs enlarged by pool_extra_width + the canonical transformation of lib/net/rcnn_net.py:151-164
+    in one launch; every element of both outputs is written (not in the reference extension; see epnet_ops.h)"""
+    px, pb, pf = dev_ptr(xyz, "xyz", _F), dev_ptr(rois, "rois", _F), dev_ptr(pts_feature, "pts_feature", _F)
+    po, pe = dev_ptr(pooled_features, "pooled_features", _F), dev_ptr(pooled_empty_flag, "pooled_empty_flag", torch.int32)
+    b, n = xyz.size(0), xyz.size(1)
+    m, c, s_num = rois.size(1), pts_feature.size(2), pooled_features.size(2)
+    need(xyz, b * n * 3, "xyz"); need(rois, b * m * 7, "rois"); need(pts_feature, b * n * c, "pts_feature")
+    need(pooled_features, b * m * s_num * (3 + c), "pooled_features"); need(pooled_empty_flag, b * m, "pooled_empty_flag")
+    with on_device_of(xyz) as s:
+        _lib.check(_lib.lib().epnet_roipool3d_canonical(b, n, m, c, s_num, float(pool_extra_width), px, pb, pf, po, pe, s),
+                   "roipool3d_canonical")
+    return 1
+
+
 # forward_slow (roipool3d.cpp:15-44) computes the same result with one thread per box; same entry here
 forward_slow = forward
 

@@ -20,6 +20,20 @@ def roipool3d_gpu(pts, pts_feature, boxes3d, pool_extra_width, sampled_pt_num=51
     return pooled_features, pooled_empty_flag
 
 
+def roipool3d_canonical_gpu(pts, pts_feature, rois, pool_extra_width, sampled_pt_num=512):
+    """roipool3d_gpu followed by the canonical transformation of the reference's eval branch (lib/net/rcnn_net.py:151-164:
+    minus the ROI centre, rotated by the ROI's ry) as one launch. pts (B,N,3), pts_feature (B,N,C), rois (B,M,7) as
+    given (not enlarged) -> (pooled_features (B,M,S,3+C), pooled_empty_flag (B,M) int32). The kernel writes every element,
+    so nothing is zero-filled first; an empty box's rows are what the reference's zero rows become under the transform."""
+    batch_size, boxes_num, feature_len = pts.shape[0], rois.shape[1], pts_feature.shape[2]
+    pooled_features = torch.empty((batch_size, boxes_num, sampled_pt_num, 3 + feature_len), dtype=torch.float32,
+                                  device=pts.device)
+    pooled_empty_flag = torch.empty((batch_size, boxes_num), dtype=torch.int32, device=pts.device)
+    roipool3d_cuda.forward_canonical(pts.contiguous(), rois.contiguous(), pts_feature.contiguous(), pool_extra_width,
+                                     pooled_features, pooled_empty_flag)
+    return pooled_features, pooled_empty_flag
+
+
 def pts_in_boxes3d_cpu(pts, boxes3d):
     """pts (N,3), boxes3d (M,7), both CPU -> list of M boolean masks (N,)"""
     if pts.is_cuda:

@@ -375,6 +375,21 @@ int epnet_rpn_proposals(int b, int n, const float *proposals, const float *score
                         void *workspace, size_t workspace_bytes, float *ret_bbox3d, float *ret_scores, int *ret_count,
                         epnet_stream_t stream);
 
+/* The end of eval_one_epoch_joint, tools/eval_rcnn.py:663-683, for all b scenes with no host synchronisation: score
+ * threshold, sort, rotated NMS, gather. boxes3d (b,m,7) decoded boxes, raw_scores / norm_scores (b,m). Per scene the
+ * candidates are the ROIs with norm_scores > score_thresh (a NaN is never one), ordered by DESCENDING raw_scores compared
+ * as floats (-0.0 == +0.0; a NaN raw score ranks before every number, as torch.sort(descending=True) places it), EQUAL
+ * scores in ASCENDING ROI index (torch.sort leaves that open; this op fixes it). Rotated NMS (nms_gpu) at nms_thresh over
+ * their BEV boxes [x - l/2, z - w/2, x + l/2, z + w/2, ry] (kitti_utils.boxes3d_to_bev_torch :137-150). Results:
+ * det_boxes3d (b,m,7) the kept boxes (copies of the input rows) and det_scores (b,m) their RAW scores in kept order, zero
+ * rows behind; det_count (b) i32 how many. A scene without a candidate gives count 0 and zero rows (the reference
+ * `continue`s, :667-668). 1 <= m <= 4096 and b <= 65535, else EPNET_ELIMIT before any launch; b == 0 returns EPNET_OK.
+ * The workspace size depends on (b, m) only. */
+size_t epnet_rcnn_detections_workspace_bytes(int b, int m);
+int epnet_rcnn_detections(int b, int m, const float *boxes3d, const float *raw_scores, const float *norm_scores,
+                          float score_thresh, float nms_thresh, void *workspace, size_t workspace_bytes,
+                          float *det_boxes3d, float *det_scores, int *det_count, epnet_stream_t stream);
+
 /* bytes of device scratch epnet_nms / epnet_nms_normal need for `boxes_num` boxes */
 size_t epnet_nms_workspace_bytes(int boxes_num);
 
@@ -404,6 +419,20 @@ int epnet_roipool3d(int batch_size, int pts_num, int boxes_num, int feature_in_l
                     int sampled_pts_num, const float *xyz, const float *boxes3d,
                     const float *pts_feature, float *pooled_features, int *pooled_empty_flag,
                     void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+
+/* roipool3d_gpu + the canonical transformation of RCNNNet.forward's eval branch (lib/net/rcnn_net.py:151-164) in ONE launch
+ * that writes every element of both outputs (no zero-fill by the caller). rois (B,M,7) are the ROIs as given: the
+ * kernel enlarges them itself for the membership test (kitti_utils.enlarge_box3d :153-163: h, w, l + 2 * extra, y + extra),
+ * so the choice of the S rows and the feature columns are exactly epnet_roipool3d's on the enlarged boxes. The xyz columns
+ * of a sampled point p for the ROI [x, y, z, h, w, l, ry] are, in fp32 and source order without contraction,
+ *   dx = p.x - x, dy = p.y - y, dz = p.z - z, c = (float)cos((double)ry), s = (float)sin((double)ry),
+ *   (dx * c + dz * (-s), dy, dx * s + dz * c)
+ * (the subtraction of :155, rotate_pc_along_y_torch :45-63). An empty box: flag 1, all S rows hold the same formula with
+ * p = 0 (what the reference's zero rows become) and 0 in the feature columns; a non-empty box: flag 0. Limits as
+ * epnet_roipool3d, checked before the launch. */
+int epnet_roipool3d_canonical(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num,
+                              float pool_extra_width, const float *xyz, const float *rois, const float *pts_feature,
+                              float *pooled_features, int *pooled_empty_flag, epnet_stream_t stream);
 
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
