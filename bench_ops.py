@@ -4,7 +4,7 @@ iou3d (rotated overlap / IoU, both NMS flavours), roipool3d, three_nn / three_in
 gradient ops, at the shapes of the reference's rcnn_online step. One JSON line per op:
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
-    python bench_ops.py [--reps 20]
+    python bench_ops.py [--reps 20] [--stage2-only | --loss-only]
 """
 import argparse
 import json
@@ -15,9 +15,217 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
+# ---- the training losses composed from stock torch calls (the comparators of epnet_amd.loss_utils) ---------------------------------
+# composed_*_loss(..., sync_free=False): the reference's structure (lib/net/train_functions.py:92-284 over lib/utils/loss_utils.py:
+# 90-350) restated on this package's surface -- boolean-mask indexing of the foreground rows (a nonzero and a device-to-host read
+# each), the host branch on fg_sum, scatter_ one-hots, cross_entropy / smooth_l1_loss means, and the .item() reads of the log.
+# sync_free=True: the same loss as masked sums over ALL rows (no indexing, no read-back): the honest alternative to a kernel.
+def _composed_box_loss(cfg, stage_cfg, names, cls_logit, pred_reg, reg_label, cls_label, reg_mask, iou_branch, ry_fine, w_cls, w_reg, w_train,
+                       fg_weight, sync_free):
+    import math
+    import torch
+    import torch.nn.functional as F
+    from epnet_amd.loss_utils import LossReturn
+    rows = cls_label.numel()
+    x = cls_logit.reshape(-1)
+    label = cls_label.reshape(-1)
+    pred_reg, reg_label = pred_reg.reshape(rows, -1), reg_label.reshape(rows, 7)
+    fg_mask = (label > 0) if reg_mask is None else (reg_mask.reshape(-1) > 0)
+    log = {}
+    # ---- classification
+    if stage_cfg.LOSS_CLS == "SigmoidFocalLoss":
+        target, pos, neg = (label > 0).float(), (label > 0).float(), (label == 0).float()
+        weights = (pos + neg) / torch.clamp(pos.sum(), min=1.0)
+        ce = torch.clamp(x, min=0) - x * target + torch.log1p(torch.exp(-torch.abs(x)))
+        prob = torch.sigmoid(x)
+        p_t = target * prob + (1 - target) * (1 - prob)
+        alpha = stage_cfg.FOCAL_ALPHA[0]
+        per = torch.pow(1.0 - p_t, stage_cfg.FOCAL_GAMMA) * (target * alpha + (1 - target) * (1 - alpha)) * ce * weights
+        loss_cls, cls_pos, cls_neg = per.sum(), (per * pos).sum(), (per * neg).sum()
+        if not sync_free:
+            log["loss_cls_pos"], log["loss_cls_neg"] = cls_pos.item(), cls_neg.item()
+    else:
+        weight = torch.where(label > 0, float(fg_weight), 1.0)
+        # the target is clamped: F.binary_cross_entropy refuses the -1 of an ignored row (a device-side assert)
+        per = F.binary_cross_entropy(torch.sigmoid(x), (label > 0).float(), weight=weight, reduction="none")
+        valid = (label >= 0).float()
+        loss_cls = (per * valid).sum() / torch.clamp(valid.sum(), min=1.0)
+        cls_pos = cls_neg = loss_cls * 0
+    # ---- regression
+    if sync_free:
+        rw = fg_mask.float() / torch.clamp(fg_mask.float().sum(), min=1.0)     # a masked mean
+        pr, lb, score, q = pred_reg, reg_label, torch.sigmoid(x), None if iou_branch is None else iou_branch.reshape(-1)
+        fg_sum = None
+    else:
+        fg_sum = fg_mask.long().sum().item()
+        if fg_sum != 0:
+            pr, lb, score = pred_reg[fg_mask], reg_label[fg_mask], torch.sigmoid(x)[fg_mask]
+            q = None if iou_branch is None else iou_branch.reshape(-1)[fg_mask]
+            rw = None
+    zero = loss_cls * 0
+    parts = dict.fromkeys(("x_bin", "z_bin", "x_res", "z_res", "y_offset", "ry_bin", "ry_res", "size", "iou", "branch"), zero)
+    if sync_free or fg_sum != 0:
+        scope, bs, nh = stage_cfg.LOC_SCOPE, stage_cfg.LOC_BIN_SIZE, stage_cfg.NUM_HEAD_BIN
+        nb = int(scope / bs) * 2
+        anchor = _anchor(cfg, pr.device)
+
+        def mean(v):
+            return v.mean() if rw is None else (v * (rw if v.dim() == 1 else rw[:, None])).sum()
+
+        def ce_mean(logits, target):
+            return F.cross_entropy(logits, target) if rw is None else (F.cross_entropy(logits, target, reduction="none") * rw).sum()
+
+        def sl1_mean(a, b):
+            return F.smooth_l1_loss(a, b) if rw is None else mean(F.smooth_l1_loss(a, b, reduction="none"))
+
+        def onehot(lab_, n):
+            o = torch.zeros((lab_.size(0), n), device=lab_.device)
+            o.scatter_(1, lab_.view(-1, 1), 1)
+            return o
+        x_shift = torch.clamp(lb[:, 0] + scope, 0, scope * 2 - 1e-3)
+        z_shift = torch.clamp(lb[:, 2] + scope, 0, scope * 2 - 1e-3)
+        x_bin, z_bin = (x_shift / bs).floor().long(), (z_shift / bs).floor().long()
+        x_res = x_shift - (x_bin.float() * bs + bs / 2)
+        z_res = z_shift - (z_bin.float() * bs + bs / 2)
+        x_hot, z_hot = onehot(x_bin, nb), onehot(z_bin, nb)
+        parts["x_bin"], parts["z_bin"] = ce_mean(pr[:, 0:nb], x_bin), ce_mean(pr[:, nb:2 * nb], z_bin)
+        parts["x_res"] = sl1_mean((pr[:, 2 * nb:3 * nb] * x_hot).sum(dim=1), x_res / bs)
+        parts["z_res"] = sl1_mean((pr[:, 3 * nb:4 * nb] * z_hot).sum(dim=1), z_res / bs)
+        o_y = 4 * nb
+        parts["y_offset"] = sl1_mean(pr[:, o_y:o_y + 1].sum(dim=1), lb[:, 1])
+        ry = lb[:, 6]
+        if ry_fine:
+            apc = (math.pi / 2) / nh
+            ry = ry % (2 * math.pi)
+            opposite = (ry > math.pi * 0.5) & (ry < math.pi * 1.5)
+            ry = torch.where(opposite, (ry + math.pi) % (2 * math.pi), ry)
+            shift = torch.clamp((ry + math.pi * 0.5) % (2 * math.pi) - math.pi * 0.25, min=1e-3, max=math.pi * 0.5 - 1e-3)
+        else:
+            apc = (2 * math.pi) / nh
+            shift = (ry % (2 * math.pi) + apc / 2) % (2 * math.pi)
+        r_bin = (shift / apc).floor().long()
+        r_res = (shift - (r_bin.float() * apc + apc / 2)) / (apc / 2)
+        r_hot = onehot(r_bin, nh)
+        o_rb, o_rr, o_sz = o_y + 1, o_y + 1 + nh, o_y + 1 + 2 * nh
+        parts["ry_bin"] = ce_mean(pr[:, o_rb:o_rr], r_bin)
+        parts["ry_res"] = sl1_mean((pr[:, o_rr:o_sz] * r_hot).sum(dim=1), r_res)
+        size_norm = pr[:, o_sz:o_sz + 3]
+        parts["size"] = sl1_mean(size_norm, (lb[:, 3:6] - anchor) / anchor) if rw is None else \
+            (F.smooth_l1_loss(size_norm, (lb[:, 3:6] - anchor) / anchor, reduction="none") * rw[:, None]).sum() / 3
+        # the consistency-enforcing IoU term
+        pred_size = size_norm * anchor + anchor
+        if cfg.TRAIN.IOU_LOSS_TYPE == "raw":
+            pred_x, pred_z = (pr[:, 2 * nb:3 * nb] * x_hot).sum(dim=1) * bs, (pr[:, 3 * nb:4 * nb] * z_hot).sum(dim=1) * bs
+            tar_x, tar_z = x_res, z_res
+        else:
+            centre = (torch.arange(nb, device=pr.device).float() * bs + bs / 2 - scope)
+            pred_x = ((centre + pr[:, 2 * nb:3 * nb] * bs) * F.softmax(pr[:, 0:nb], 1)).sum(dim=1)
+            pred_z = ((centre + pr[:, 3 * nb:4 * nb] * bs) * F.softmax(pr[:, nb:2 * nb], 1)).sum(dim=1)
+            tar_x, tar_z = centre[x_bin] + x_res, centre[z_bin] + z_res
+        pred_y = pr[:, o_y:o_y + 1].sum(dim=1)
+
+        def overlap(pc, pe, tc, te):
+            return torch.clamp(torch.min(pc + pe / 2, tc + te / 2) - torch.max(pc - pe / 2, tc - te / 2), min=1e-3)
+        inter = overlap(pred_x, pred_size[:, 2], tar_x, lb[:, 5]) * overlap(pred_y, pred_size[:, 0], lb[:, 1], lb[:, 3]) * \
+            overlap(pred_z, pred_size[:, 1], tar_z, lb[:, 4])
+        pred_vol = torch.clamp(pred_size[:, 0] * pred_size[:, 1] * pred_size[:, 2], min=1e-3)
+        iou = inter / (pred_vol + lb[:, 3] * lb[:, 4] * lb[:, 5] - inter)
+        if q is not None:
+            qc, tg = torch.clamp(q, 0.0001, 0.9999), torch.clamp(iou, 0.0001, 0.9999).detach()
+            parts["branch"] = mean(-(tg * torch.log(qc) + (1 - tg) * torch.log(1 - qc)))
+        parts["iou"] = mean(-torch.log(torch.clamp(score * iou, min=1e-4)))
+        if not sync_free:
+            for k in ("x_bin", "z_bin", "x_res", "z_res", "y_offset", "ry_bin", "ry_res"):
+                log[k] = parts[k].item()                                        # reg_loss_dict's .item()s
+    loss_loc = parts["x_bin"] + parts["z_bin"] + parts["x_res"] + parts["z_res"] + parts["y_offset"]
+    loss_angle = parts["ry_bin"] + parts["ry_res"]
+    loss_size, loss_iou = 3 * parts["size"], cfg.TRAIN.CE_WEIGHT * parts["iou"]
+    loss_reg = loss_loc + loss_angle + loss_size + loss_iou + parts["branch"]
+    loss = loss_cls * w_cls + loss_reg * w_reg
+    total = loss * w_train
+    pos_n, neg_n, valid_n = (label > 0).sum(), (label == 0).sum(), (label >= 0).sum()
+    entries = [total, loss, loss_cls, cls_pos, cls_neg, loss_reg, loss_loc, loss_angle, loss_size, loss_iou, parts["x_bin"], parts["z_bin"],
+               parts["x_res"], parts["z_res"], parts["y_offset"], parts["ry_bin"], parts["ry_res"], parts["branch"],
+               fg_mask.sum(), pos_n, neg_n, valid_n, parts["size"], parts["iou"]]
+    if not sync_free:                                                           # tb_dict / disp_dict: one .item() per entry
+        for k, v in zip(names, entries):
+            log[k] = v.item()
+    terms = torch.stack([e.detach().float().reshape(()) for e in entries])
+    return LossReturn(total, terms, names)
+
+
+_anchors = {}
+
+
+def _anchor(cfg, device):
+    import torch
+    if str(device) not in _anchors:
+        _anchors[str(device)] = torch.from_numpy(cfg.CLS_MEAN_SIZE[0]).to(device)
+    return _anchors[str(device)]
+
+
+def composed_rpn_loss(rpn_cls, rpn_reg, rpn_cls_label, rpn_reg_label, cfg=None, sync_free=False):
+    from epnet_amd import loss_utils
+    cfg = cfg if cfg is not None else loss_utils.default_cfg()
+    return _composed_box_loss(cfg, cfg.RPN, loss_utils.RPN_TERM_NAMES, rpn_cls, rpn_reg, rpn_reg_label, rpn_cls_label, None, None, False,
+                              cfg.RPN.LOSS_WEIGHT[0], cfg.RPN.LOSS_WEIGHT[1], cfg.TRAIN.RPN_TRAIN_WEIGHT, cfg.RPN.FG_WEIGHT, sync_free)
+
+
+def composed_rcnn_loss(ret_dict, cfg=None, sync_free=False):
+    from epnet_amd import loss_utils
+    cfg = cfg if cfg is not None else loss_utils.default_cfg()
+    return _composed_box_loss(cfg, cfg.RCNN, loss_utils.RCNN_TERM_NAMES, ret_dict["rcnn_cls"], ret_dict["rcnn_reg"], ret_dict["gt_of_rois"],
+                              ret_dict["cls_label"], ret_dict["reg_valid_mask"], ret_dict["rcnn_iou_branch"] if cfg.USE_IOU_BRANCH else None,
+                              True, 1.0, 1.0, cfg.TRAIN.RCNN_TRAIN_WEIGHT, 1.0, sync_free)
+
+
+def loss_rows(args, report, timeit_pair):
+    """forward + backward of the fused losses against (i) the reference-shaped composition and (ii) the sync-free stock-torch form,
+    at the RPN shapes (scenes x 16384 points x 76, labels from the synthetic scenes' ground-truth boxes) and the RCNN shapes
+    (scenes x 64 ROIs x 46)"""
+    import torch
+    import bench_step
+    from epnet_amd import loss_utils
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(3)
+    for bsz in (1, 2, 16):
+        xyz, gts = bench_step.synthetic_batch(bsz, 16384, 300, dev)
+        cls_label, reg_label = bench_step.rpn_labels(xyz, gts)
+        rpn_cls = (torch.randn((bsz, 16384, 1), generator=g) * 1.5).to(dev).requires_grad_(True)
+        rpn_reg = (torch.randn((bsz, 16384, 76), generator=g) * 0.5).to(dev).requires_grad_(True)
+        u = torch.rand((bsz * 64,), generator=g).to(dev)
+        ret = {"rcnn_cls": (torch.randn((bsz * 64, 1), generator=g) * 1.5).to(dev).requires_grad_(True),
+               "rcnn_reg": (torch.randn((bsz * 64, 46), generator=g) * 0.5).to(dev).requires_grad_(True),
+               "cls_label": torch.where(u > 0.6, 1, torch.where(u < 0.45, 0, -1)).long(), "reg_valid_mask": (u > 0.55).long(),
+               "gt_of_rois": torch.cat([(torch.rand((bsz * 64, 3), generator=g) - 0.5) * 2, torch.tensor([1.5, 1.6, 3.9]) * (0.9 + 0.2 * torch.rand((bsz * 64, 3), generator=g)),
+                                        torch.rand((bsz * 64, 1), generator=g) * 6.28], dim=1).to(dev)}
+        for stage, rows, c, leaves, fns in (
+                ("rpn", bsz * 16384, 76, [rpn_cls, rpn_reg], [lambda sf=None: loss_utils.rpn_loss(rpn_cls, rpn_reg, cls_label, reg_label) if sf is None
+                                                              else composed_rpn_loss(rpn_cls, rpn_reg, cls_label, reg_label, sync_free=sf)]),
+                ("rcnn", bsz * 64, 46, [ret["rcnn_cls"], ret["rcnn_reg"]], [lambda sf=None: loss_utils.rcnn_loss(ret) if sf is None
+                                                                            else composed_rcnn_loss(ret, sync_free=sf)])):
+            fn = fns[0]
+
+            def run(sf):
+                out = fn(sf)
+                torch.autograd.grad(out.loss, leaves, allow_unused=True)
+                return out
+            fused, ref_shaped, sync_free = (lambda: run(None)), (lambda: run(False)), (lambda: run(True))
+            a, b, c_ = fused(), ref_shaped(), sync_free()
+            close = bool(torch.allclose(a.terms, b.terms, rtol=1e-4, atol=1e-5) and torch.allclose(a.terms, c_.terms, rtol=1e-4, atol=1e-5))
+            ms_ref, ms_fused = timeit_pair(ref_shaped, fused)
+            ms_free, ms_fused2 = timeit_pair(sync_free, fused)
+            report("%s_loss fwd+bwd" % stage, {"scenes": bsz, "rows": rows, "C": c, "fg": int(a.terms[18])}, ms_fused,
+                   rows * (c * 8 + 7 * 4 + 4 + 8),
+                   "one fused call + backward scaling; (i) reference-shaped composition (mask indexing, .item() reads): %.4f ms; (ii) sync-free "
+                   "stock-torch form (masked sums): %.4f ms (fused in that pair: %.4f ms); same terms within 1e-4: %s"
+                   % (ms_ref, ms_free, ms_fused2, close))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--loss-only", action="store_true", help="only the training-loss rows (fused against the two stock-torch forms)")
     ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
     args = ap.parse_args()
     import torch
@@ -129,6 +337,8 @@ def main():
 
     if args.stage2_only:
         return stage2_infer()
+    if args.loss_only:
+        return loss_rows(args, report, timeit_pair)
     # ---- NMS at the proposal-layer sizes (RPN.NMS_TYPE normal, N <= 6300 / 2700, thresh 0.85) and eval rotated NMS
     for n, rot, thr in ((6300, False, 0.85), (2700, False, 0.85), (6300, True, 0.8), (512, True, 0.1), (100, True, 0.1)):
         boxes, scores = synth.proposal_boxes(n, seed=n, num_objects=40, jitter=1.5)
@@ -321,6 +531,7 @@ def main():
         ms = timeit(lambda: p2.group_concat_wrapper(bsz, 0, n, m, ns, xyz, new_xyz, None, bq, gx, True))
         report("group_concat", {"B": bsz, "C": 0, "N": n, "M": m, "ns": ns}, ms, bsz * (m * ns * 4 + 3 * n * 4 + 3 * m * ns * 4))
     stage2_infer()
+    loss_rows(args, report, timeit_pair)
 
 
 if __name__ == "__main__":

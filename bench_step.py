@@ -19,8 +19,9 @@ Every geometry op is this package's HIP path; every dense layer (shared MLPs, ba
 fusion, heads, optimiser) is stock PyTorch-ROCm, as the north_star has it. With --image the backbone is the two-stream one
 (epnet_amd/rpn_backbone.py = lib/net/pointnet2_msg.py: four strided conv blocks over a (B,3,384,1280) image ~N(0,1),
 Feature_Gather at the four pyramid levels and at full resolution, attention fusion); pixel coordinates ~U[0,1280)xU[0,384).
-Losses are placeholders (sums of squares) -- the step exercises autograd through every op of the hot path at the real
-shapes, it does not train anything. `ops_share` = HIP-event time inside this package's operators / the step's GPU time,
+Losses are placeholders (sums of squares) by default -- the step exercises autograd through every op of the hot path at the
+real shapes, it does not train anything; `--loss reference` ends the step in the real RPN + RCNN losses (epnet_amd.loss_utils, one
+fused call each) on labels built from the synthetic boxes, `--loss composed` in the same losses composed from stock torch calls. `ops_share` = HIP-event time inside this package's operators / the step's GPU time,
 from an instrumented pass after the timed one. With N > 1 ranks the model is wrapped
 in DistributedDataParallel: the gradient all-reduce over RCCL / xGMI is the step's only collective (scenes are sharded
 by rank). One JSON line from rank 0.
@@ -45,9 +46,12 @@ RCNN_NPOINTS, RCNN_RADIUS, RCNN_NSAMPLE = [128, 32, None], [0.2, 0.4, 100], [64,
 RCNN_MLPS = [[128, 128, 128], [128, 128, 256], [256, 256, 512]]
 
 
-def build_model(scale=1, rpn_channels=76, image=False, sampler="hip"):
+def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder"):
     """the two-stage model; scale > 1 divides the pyramid's point counts (small test configurations); image: the
-    two-stream backbone with LI-Fusion (configs 3 / 4) instead of the point stream alone"""
+    two-stream backbone with LI-Fusion (configs 3 / 4) instead of the point stream alone; loss: "placeholder" (sums of squares),
+    "reference" (the real losses, fused: epnet_amd.loss_utils) or "composed" (the real losses as the reference composes them from
+    stock torch calls, with its mask indexing and .item() reads: bench_ops.composed_rpn_loss / composed_rcnn_loss); the real
+    losses read the RPN labels from model.rpn_labels = rpn_labels(xyz, gt_boxes3d)"""
     import torch
     import torch.nn as nn
     from epnet_amd import pytorch_utils as pt_utils, rpn_backbone
@@ -89,6 +93,8 @@ def build_model(scale=1, rpn_channels=76, image=False, sampler="hip"):
             self.rpn_reg = nn.Sequential(pt_utils.Conv1d(128, 128, bn=True), pt_utils.Conv1d(128, rpn_channels, activation=None))
             self.rcnn = RCNN()
             self.layers = None   # (ProposalLayer, ProposalTargetLayer), set by the caller
+            self.loss_mode = loss
+            self.rpn_labels = None   # (cls_label (B,N), reg_label (B,N,7)) for the real losses, set by the caller
 
         def forward(self, xyz, gt_boxes3d, mark=None, image=None, xy=None, rpn_only=False):
             """one forward pass + placeholder loss (the whole step lives in forward so that DistributedDataParallel sees
@@ -100,7 +106,16 @@ def build_model(scale=1, rpn_channels=76, image=False, sampler="hip"):
             rpn_cls = self.rpn_cls(feats).transpose(1, 2).contiguous()           # (B,N,1)
             rpn_reg = self.rpn_reg(feats).transpose(1, 2).contiguous()           # (B,N,76)
             mark("rpn")
-            if rpn_only:                                                         # config 3: backbone + heads, dummy loss
+            real = self.loss_mode != "placeholder"
+            if real:                                                             # lib/net/train_functions.py:51-67
+                if self.loss_mode == "reference":
+                    from epnet_amd.loss_utils import rpn_loss, rcnn_loss
+                else:
+                    from bench_ops import composed_rpn_loss as rpn_loss, composed_rcnn_loss as rcnn_loss
+                loss_rpn = rpn_loss(rpn_cls, rpn_reg, self.rpn_labels[0], self.rpn_labels[1])
+            if rpn_only:                                                         # config 3: backbone + heads
+                if real:
+                    return loss_rpn.loss, {"rpn_cls": rpn_cls, "rpn_reg": rpn_reg, "rpn_loss": loss_rpn}
                 return rpn_cls.pow(2).mean() + rpn_reg.pow(2).mean(), {"rpn_cls": rpn_cls, "rpn_reg": rpn_reg}
             with torch.no_grad():                                                # lib/net/point_rcnn.py:33-47
                 scores = rpn_cls[:, :, 0].detach()
@@ -114,6 +129,11 @@ def build_model(scale=1, rpn_channels=76, image=False, sampler="hip"):
                 mark("targets")
             rcnn_cls, rcnn_reg = self.rcnn(target["sampled_pts"], target["pts_feature"])
             mark("rcnn")
+            if real:                                                             # lib/net/train_functions.py:69-88
+                loss_rcnn = rcnn_loss(dict(target, rcnn_cls=rcnn_cls.view(rcnn_cls.shape[0], -1), rcnn_reg=rcnn_reg.view(rcnn_reg.shape[0], -1)))
+                mark("losses")
+                return loss_rpn.loss + loss_rcnn.loss, {"rois": rois, "target": target, "rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg,
+                                                        "rpn_cls": rpn_cls, "rpn_reg": rpn_reg, "rpn_loss": loss_rpn, "rcnn_loss": loss_rcnn}
             loss = rpn_cls.pow(2).mean() + rpn_reg.pow(2).mean() + rcnn_cls.pow(2).mean() + rcnn_reg.pow(2).mean()
             return loss, {"rois": rois, "target": target, "rcnn_cls": rcnn_cls, "rcnn_reg": rcnn_reg}
 
@@ -124,6 +144,33 @@ def run_step(model, layers, xyz, gt_boxes3d, timer=None, image=None, xy=None, rp
     """one forward pass through `model` (plain or DistributedDataParallel-wrapped)"""
     (model.module if hasattr(model, "module") else model).layers = layers
     return model(xyz, gt_boxes3d, timer, image, None if xy is None else xy.clone(), rpn_only)
+
+
+def rpn_labels(xyz, gt_boxes3d, inside=0.05, ignore=0.2):
+    """per-point RPN labels as the reference's loader makes them on the host (lib/datasets/kitti_rcnn_dataset.py,
+    generate_rpn_training_labels), here from the synthetic scenes' own boxes, on the device and outside every timed region:
+    cls_label (B,N) 1 for a point in a ground-truth box, -1 in the box enlarged by `ignore` but not in it, else 0; reg_label
+    (B,N,7) [centre - point, h, w, l, ry] for the labelled points, zero elsewhere. The synthetic object points lie ON the
+    faces of their boxes, so a box counts as enlarged by `inside` already. xyz (B,N,3), gt_boxes3d (B,G,7) zero-padded"""
+    import torch
+    centre = gt_boxes3d[:, None, :, 0:3].clone()
+    centre[..., 1] -= gt_boxes3d[:, None, :, 3] / 2
+    d = xyz[:, :, None, :] - centre                                             # (B,N,G,3)
+    ry = gt_boxes3d[:, None, :, 6]
+    lx = d[..., 0] * torch.cos(ry) - d[..., 2] * torch.sin(ry)
+    lz = d[..., 0] * torch.sin(ry) + d[..., 2] * torch.cos(ry)
+    h, w, l = (gt_boxes3d[:, None, :, k] for k in (3, 4, 5))
+    real = (h > 0)
+
+    def within(extra):
+        return real & (lx.abs() <= l / 2 + extra) & (lz.abs() <= w / 2 + extra) & (d[..., 1].abs() <= h / 2 + extra)
+    fg_any, which = within(inside).int().max(dim=2)
+    fg_any = fg_any > 0
+    cls_label = torch.where(fg_any, 1, torch.where(within(ignore).any(dim=2), -1, 0)).long()
+    pick = which[:, :, None, None].expand(-1, -1, 1, 3)
+    reg = torch.cat([-torch.gather(d, 2, pick)[:, :, 0], torch.gather(gt_boxes3d[:, None].expand(-1, xyz.shape[1], -1, -1), 2,
+                                                                        which[:, :, None, None].expand(-1, -1, 1, 7))[:, :, 0, 3:7]], dim=2)
+    return cls_label.contiguous(), (reg * fg_any[:, :, None]).contiguous()
 
 
 def synthetic_batch(batch, points, seed, device):
@@ -231,6 +278,10 @@ def main():
     ap.add_argument("--rpn-only", action="store_true", help="config 3: forward + backward of backbone + RPN heads only")
     ap.add_argument("--sampler", default="hip", choices=["hip", "stock"],
                     help="point-to-pixel sampler: this package's Feature_Gather or stock torch.gather + grid_sample")
+    ap.add_argument("--loss", default="placeholder", choices=["placeholder", "reference", "composed"],
+                    help="the step's loss: sums of squares (default), the real RPN + RCNN losses fused (epnet_amd.loss_utils), or the "
+                         "real losses composed from stock torch calls as the reference does, mask indexing and .item() reads included; "
+                         "the RPN labels are built on the device outside the timed region")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without a torch.distributed.run environment the ranks are started as child processes")
     ap.add_argument("--launch-check", action="store_true", help="rehearse the N-rank launch only (see bench.py)")
@@ -269,7 +320,7 @@ def main():
             dist.init_process_group(backend)
     torch.manual_seed(1 + rank)
     np.random.seed(1 + rank)
-    model = build_model(image=args.image, sampler=args.sampler).to(device)
+    model = build_model(image=args.image, sampler=args.sampler, loss=args.loss).to(device)
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local], find_unused_parameters=False)
     opt = torch.optim.SGD(model.parameters(), lr=1e-4, momentum=0.9)
@@ -283,8 +334,11 @@ def main():
 
     if args.infer:
         return infer(args, model.module if hasattr(model, "module") else model, layers[0], xyz)
+    if args.loss != "placeholder":
+        (model.module if hasattr(model, "module") else model).rpn_labels = rpn_labels(xyz, gts)
 
     phases = {}
+    last_out = {}
 
     def one(timed):
         events = [("start", torch.cuda.Event(enable_timing=True))]
@@ -295,7 +349,9 @@ def main():
             e.record()
             events.append((name, e))
         opt.zero_grad(set_to_none=True)
-        loss, _ = run_step(model, layers, xyz, gts, mark if timed else None, image, xy, args.rpn_only)
+        loss, out = run_step(model, layers, xyz, gts, mark if timed else None, image, xy, args.rpn_only)
+        if timed:                                              # the line carries the terms of the last TIMED step
+            last_out.update({k: v for k, v in out.items() if k in ("rpn_loss", "rcnn_loss")})
         loss.backward()
         mark("backward")
         opt.step()
@@ -405,6 +461,8 @@ def main():
                           "per_rank_ms_per_step": {"min": min(r_["ms_per_step"] for r_ in per_rank),
                                                    "max": max(r_["ms_per_step"] for r_ in per_rank)},
                           "loss": last, "data": "synthetic", "dtype": "f32",
+                          **({} if args.loss == "placeholder" else {"loss_mode": args.loss, "loss_terms": {
+                              n_: round(float(v), 6) for r_ in last_out.values() for n_, v in zip(r_.names, r_.terms.tolist())}}),
                           "note": "phase_ms from HIP events (phases are host-serialised by the two syncs of the target layer); "
                                   "dense layers are stock PyTorch-ROCm, geometry ops this package's HIP kernels"}))
     if world > 1:

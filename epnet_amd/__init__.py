@@ -10,6 +10,9 @@ The package holds only what the hot path needs:
 * ``pointnet2_utils``, ``pointnet2_modules``, ``pytorch_utils``, ``iou3d_utils``,
   ``roipool3d_utils``, ``kitti_utils``
                      the reference's Python operator surface, re-provided with identical names
+* ``loss_cuda``, ``loss_utils``
+                     the training losses (``lib/net/train_functions.py``'s two closures) as one fused call each, forward
+                     and backward, with no host synchronisation
 * ``compat``         registers all of the above under the import paths the reference's callers use
 * ``synth``, ``sa_stack``  synthetic KITTI-shaped inputs and the SA/FP op-stack driver used by bench.py
 

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("EPNET_HIP_LIB") or os.path.join(_HERE, "lib", "libepn
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
+_d = ctypes.c_double
 _sz = ctypes.c_size_t
 _i64 = ctypes.c_int64
 
@@ -91,6 +92,9 @@ SIGNATURES = {
     "epnet_roipool3d_workspace_bytes": (_sz, [_i, _i, _i]),
     "epnet_roipool3d": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "epnet_roipool3d_canonical": (_i, [_i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_box_loss_workspace_bytes": (_sz, [ctypes.c_longlong, _i]),
+    "epnet_box_loss": (_i, [ctypes.c_longlong, _i, _d, _d, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "epnet_pts_in_boxes3d_host": (_i, [_vp, _vp, _vp, _i64, _i64]),
     "epnet_roipool3d_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64]),
 }

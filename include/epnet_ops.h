@@ -434,6 +434,44 @@ int epnet_roipool3d_canonical(int batch_size, int pts_num, int boxes_num, int fe
                               float pool_extra_width, const float *xyz, const float *rois, const float *pts_feature,
                               float *pooled_features, int *pooled_empty_flag, epnet_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * training losses (lib/net/train_functions.py:92-284 over lib/utils/loss_utils.py:79-350)
+ * -------------------------------------------------------------------------------------- */
+
+/* get_rpn_loss / get_rcnn_loss with get_reg_loss and the classification loss, forward and backward in one call, for `rows`
+ * rows (points of the RPN, ROIs of the RCNN stage) with no host synchronisation: the reference selects the foreground rows by
+ * boolean masks, branches on their count on the host and reads some 25 scalars back per step.
+ * pred_reg (rows, c), c = 4 nb + 1 + 2 num_head_bin + 3 with nb = (int)(loc_scope / loc_bin_size) * 2, columns
+ * [x_bin nb | z_bin nb | x_res nb | z_res nb | y_offset | ry_bin nh | ry_res nh | size 3] (get_xz_fine, y by offset);
+ * cls_logit (rows); reg_label (rows, 7) [dx, dy, dz, h, w, l, ry]; cls_label (rows) i32: -1 ignored, 0 negative, > 0 positive;
+ * reg_mask (rows) i32 or NULL: the foreground rows are reg_mask > 0 (NULL: cls_label > 0); iou_branch_pred (rows) or NULL:
+ * the USE_IOU_BRANCH term (loss_utils.py:263-269); anchor (3) = CLS_MEAN_SIZE; ry_fine: get_ry_fine (RCNN) or not (RPN).
+ * Regression terms are sums over the foreground rows divided by max(count, 1): without a foreground row they are exactly 0
+ * with zero gradients. The scalars are those of the Python calls (doubles that meet fp32 tensors).
+ *   terms (EPNET_BOX_LOSS_TERMS floats), in this order: total = loss * w_train; loss = loss_cls * w_cls + loss_reg * w_reg;
+ *     loss_cls, its positive and negative parts (focal only); loss_reg = loc + angle + size + iou + iou_branch; loss_loc;
+ *     loss_angle; loss_size (x 3); loss_iou (x ce_weight); loss_x_bin, z_bin, x_res, z_res, y_offset, ry_bin, ry_res;
+ *     iou_branch_loss; the counts of foreground, positive, negative and valid (label >= 0) rows as floats (exact below 2^24);
+ *     loss_size and loss_iou without the callers' weights (the entries of reg_loss_dict).
+ *   grad_cls (rows), grad_reg (rows, c), grad_iou_branch (rows; NULL exactly when iou_branch_pred is): d total / d input,
+ *     every element written (zero rows for background).
+ * Sums over rows are folded in a fixed order without float atomics: the bits depend on the inputs and the shape alone.
+ * workspace: 16-byte aligned, epnet_box_loss_workspace_bytes(rows, c) = 4096 + ceil(rows / 64) * 64 bytes. nb and
+ * num_head_bin up to 32, else EPNET_ELIMIT; rows == 0 returns EPNET_OK and writes nothing. */
+#define EPNET_BOX_LOSS_TERMS 24
+#define EPNET_LOSS_IOU_RAW 0
+#define EPNET_LOSS_IOU_CLS_MASK_WITH_BIN 1
+#define EPNET_LOSS_CLS_FOCAL 0  /* SigmoidFocalLoss: weights (pos + neg) / max(sum pos, 1), focal_alpha, focal_gamma */
+#define EPNET_LOSS_CLS_BCE 1    /* BinaryCrossEntropy: fg_weight on the positive rows, mean over the valid rows */
+#define EPNET_LOSS_CLS_NONE 2   /* no classification term (the caller adds its own, e.g. DiceLoss) */
+size_t epnet_box_loss_workspace_bytes(long long rows, int c);
+int epnet_box_loss(long long rows, int c, double loc_scope, double loc_bin_size, int num_head_bin, int ry_fine,
+                   int iou_loss_type, int cls_loss_type, double focal_alpha, double focal_gamma, double fg_weight,
+                   double w_cls, double w_reg, double w_train, double ce_weight, const float *cls_logit,
+                   const float *pred_reg, const float *reg_label, const int *cls_label, const int *reg_mask,
+                   const float *iou_branch_pred, const float *anchor, float *terms, float *grad_cls, float *grad_reg,
+                   float *grad_iou_branch, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
