@@ -4,7 +4,7 @@ iou3d (rotated overlap / IoU, both NMS flavours), roipool3d, three_nn / three_in
 gradient ops, at the shapes of the reference's rcnn_online step. One JSON line per op:
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
-    python bench_ops.py [--reps 20] [--stage2-only | --loss-only]
+    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only]
 """
 import argparse
 import json
@@ -222,10 +222,60 @@ def loss_rows(args, report, timeit_pair):
                    % (ms_ref, ms_free, ms_fused2, close))
 
 
+def targets_rows(args, report, timeit_pair):
+    """the fused RPN training targets (augmentation + labels, one launch: epnet_amd/rpn_target_layer.py) against the stock
+    composition bench_step.rpn_labels (labels only, (B,N,G,3) temporaries), alternating inside one call, at 2 / 16 / 256 scenes x
+    16384 points x 20 box rows (12 real). The composition runs in chunks of scenes if it runs out of memory."""
+    import torch
+    import bench_step
+    from epnet_amd import rpn_target_layer as rtl
+    dev = torch.device("cuda:0")
+    n, peak = 16384, 8e12
+    for bsz in (2, 16, 256):
+        xyz, gts = bench_step.synthetic_batch(bsz, n, 300, dev)
+        g = gts.shape[1]
+        alpha = (torch.rand((bsz, g), generator=torch.Generator().manual_seed(7)) * 6.28 - 3.14).to(dev) * (gts[:, :, 3] > 0)
+        aug = rtl.draw_augmentation(bsz, rtl.default_cfg(), torch.Generator(device=dev).manual_seed(9), device=dev)
+        chunk = [bsz]
+
+        def composed():
+            return [bench_step.rpn_labels(xyz[i:i + chunk[0]], gts[i:i + chunk[0]]) for i in range(0, bsz, chunk[0])]
+
+        def fused():
+            return rtl.augment_and_label(xyz, gts, alpha, aug)
+
+        def labels_only():
+            return rtl.rpn_training_labels(xyz, gts)
+        while True:
+            try:
+                want = composed()
+                break
+            except torch.OutOfMemoryError:
+                want = None
+                torch.cuda.empty_cache()
+                chunk[0] = max(1, chunk[0] // 2)
+        # how often the two rules give the same class on the unaugmented cloud (they are different rules: the synthetic object
+        # points lie ON the faces, where the composition counts a box as enlarged by 0.05 already; see bench_step.rpn_labels)
+        cls, reg = labels_only()
+        agree = float((torch.cat([w[0] for w in want]).view(-1) == cls.view(-1).long()).float().mean())
+        counts = {k: int((cls == v).sum()) for k, v in (("fg", 1), ("ignored", -1))}
+        counts["ignored_with_row"] = int(((cls == -1) & (reg.abs().sum(dim=2) > 0)).sum())
+        del want
+        ms_c, ms_f = timeit_pair(composed, fused)
+        ms_c2, ms_l = timeit_pair(composed, labels_only)
+        nbytes = bsz * n * 56 + bsz * g * 56
+        report("rpn_targets", dict({"scenes": bsz, "N": n, "G": g}, **counts), ms_f, nbytes,
+               "augmentation + labels, one launch, no host sync: %.3f of the 8 TB/s peak over B*N*56 + B*G*56 bytes; labels alone "
+               "(no aug table, 44 bytes per point): %.4f ms; stock composition bench_step.rpn_labels (labels only, another rule, in chunks "
+               "of %d scenes): %.4f ms (%.4f ms in the second pair); same class on %.4f of the points"
+               % (nbytes / (ms_f * 1e-3) / peak, ms_l, chunk[0], ms_c, ms_c2, agree))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--loss-only", action="store_true", help="only the training-loss rows (fused against the two stock-torch forms)")
+    ap.add_argument("--targets-only", action="store_true", help="only the RPN training targets (fused against bench_step.rpn_labels)")
     ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
     args = ap.parse_args()
     import torch
@@ -339,6 +389,8 @@ def main():
         return stage2_infer()
     if args.loss_only:
         return loss_rows(args, report, timeit_pair)
+    if args.targets_only:
+        return targets_rows(args, report, timeit_pair)
     # ---- NMS at the proposal-layer sizes (RPN.NMS_TYPE normal, N <= 6300 / 2700, thresh 0.85) and eval rotated NMS
     for n, rot, thr in ((6300, False, 0.85), (2700, False, 0.85), (6300, True, 0.8), (512, True, 0.1), (100, True, 0.1)):
         boxes, scores = synth.proposal_boxes(n, seed=n, num_objects=40, jitter=1.5)

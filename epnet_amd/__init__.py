@@ -13,6 +13,9 @@ The package holds only what the hot path needs:
 * ``loss_cuda``, ``loss_utils``
                      the training losses (``lib/net/train_functions.py``'s two closures) as one fused call each, forward
                      and backward, with no host synchronisation
+* ``rpn_target_cuda``, ``rpn_target_layer``
+                     the RPN training targets (the loader's augmentation and per-point labels) of a whole batch as one
+                     launch, with no host synchronisation
 * ``compat``         registers all of the above under the import paths the reference's callers use
 * ``synth``, ``sa_stack``  synthetic KITTI-shaped inputs and the SA/FP op-stack driver used by bench.py
 

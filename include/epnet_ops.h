@@ -472,6 +472,40 @@ int epnet_box_loss(long long rows, int c, double loc_scope, double loc_bin_size,
                    const float *iou_branch_pred, const float *anchor, float *terms, float *grad_cls, float *grad_reg,
                    float *grad_iou_branch, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * RPN training targets (lib/datasets/kitti_rcnn_dataset.py:378-408: data_augmentation :698-755,
+ * generate_rpn_training_labels :547-576)
+ * -------------------------------------------------------------------------------------- */
+
+/* The loader's augmentation and per-point RPN labels of a whole batch in ONE launch with no host synchronisation: the
+ * reference runs them per scene on a host core (two scipy Delaunay point-in-hull tests per box over all points).
+ * pts (b,n,3); gt_boxes3d (b,g,7) [x,y,z,h,w,l,ry], zero-padded as collate_batch pads; gt_alpha (b,g), zero where the row is
+ * padding (NULL allowed when aug is NULL); aug (b,4) = [rotate 0/1, angle, scale, flip 0/1] per scene, or NULL for no augmentation; extra_width >= 0: the
+ * ignore margin (the reference uses 0.2).
+ * Augmentation, per scene, in the reference's order (stage 1): with rotate != 0, x' = x cos a - z sin a, z' = x sin a +
+ * z cos a for the points and the box centres, evaluated in double from the fp32 inputs and the angle and rounded once
+ * (rotate_pc_along_y's float64 np.dot), then ry' = sign(beta) * pi / 2 + gt_alpha - beta with beta = atan2(z', x') in fp32
+ * (with rotate == 0 the incoming ry is kept: a rotation by 0 is not the identity on ry); all point coordinates and box
+ * columns 0..5 times scale in fp32 (1 = off); with flip != 0, x = -x and ry = sign(ry) * pi - ry. Zero rows stay zero.
+ * Labels, from the augmented values: a row is a box when h, w and l are all > 0. With c = (x, y - h/2, z), d = p - c,
+ * lx = d.x cos ry + d.z (-sin ry), lz = d.x sin ry + d.z cos ry (fp32, source order, no contraction; cos / sin correctly
+ * rounded via double, as epnet_roipool3d's predicate), a point is in the box when |lx| <= l/2, |d.y| <= h/2, |lz| <= w/2 and
+ * in the enlarged box (kitti_utils.enlarge_box3d: h, w, l + 2 extra_width about the same centre) when the same holds with
+ * (l + 2e)/2, (h + 2e)/2, (w + 2e)/2. With the boxes in ascending row order, as the reference's loop:
+ *   cls_label (b,n) i32: decided by the LAST box whose enlarged form holds the point -- 1 if that box itself holds it, else
+ *     -1; 0 if none does;
+ *   reg_label (b,n,7): decided by the LAST box that holds the point, independently of the class (a later box's margin may
+ *     turn the class to -1 and the row stays): [c - p, h, w, l, ry]; zeros if none does.
+ * A NaN coordinate is in no box: class 0, zero row. g == 0 is valid (all labels zero); any g works (the kernel takes the
+ * boxes 64 at a time). pts_out (b,n,3) and gt_out (b,g,7) receive the augmented values; both may be NULL when aug is NULL
+ * (given there, they receive copies). Every element of every output is written. No atomics: the bits depend on the inputs
+ * alone. PRECONDITION: no output may alias an input (pts_out != pts, gt_out != gt_boxes3d; every workgroup of a scene
+ * reads all of that scene's box rows). b == 0 or n == 0 returns EPNET_OK and writes nothing; b > 65535 is EPNET_ELIMIT
+ * before any launch. */
+int epnet_rpn_targets(int b, int n, int g, float extra_width, const float *pts, const float *gt_boxes3d,
+                      const float *gt_alpha, const float *aug, float *pts_out, float *gt_out, int *cls_label,
+                      float *reg_label, epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
