@@ -447,6 +447,96 @@ __device__ __forceinline__ void bq_emit_list(int lane, const int *hits, int cnt,
     for (int l = cnt + lane; l < nsample; l += 64) out[l] = first;
 }
 
+// ---- shared lists: the two scales of an MSG level (nested balls) keep ONE list per centre ----
+// An entry is (original index << 1) | (also inside the smaller ball): the indices are distinct, so the entries order as their
+// indices do, and the low bit says which of them the smaller scale wants.
+
+// one centre, <= 64 entries in `hits`: both scales from one rank loop (the path of an odd list length above the pair bound)
+__device__ __forceinline__ void bq_emit_shared(int lane, const int *hits, int cnt, int ns_big, int ns_small, int *__restrict__ out_big,
+                                               int *__restrict__ out_small) {
+    __builtin_amdgcn_wave_barrier();
+    const bool valid = lane < cnt;
+    const int mine = valid ? hits[lane] : 0x7fffffff;
+    int rank = 0, rin = 0;   // smaller entries among all / among the inner ones
+    for (int j = 0; j < cnt; ++j) {
+        const int v = __builtin_amdgcn_readlane(mine, j);
+        rank += v < mine ? 1 : 0;
+        rin += v < mine ? (v & 1) : 0;
+    }
+    const bool inner = valid && (mine & 1);
+    if (valid && rank < ns_big) out_big[rank] = mine >> 1;
+    if (inner && rin < ns_small) out_small[rin] = mine >> 1;
+    int first = 0;
+    if (cnt) first = __builtin_amdgcn_readlane(mine, (int)__builtin_ctzll(__ballot(valid && rank == 0))) >> 1;
+    for (int l = cnt + lane; l < ns_big; l += 64) out_big[l] = first;
+    const unsigned long long im = __ballot(inner);
+    const int cin = (int)__popcll(im);
+    first = 0;
+    if (cin) first = __builtin_amdgcn_readlane(mine, (int)__builtin_ctzll(__ballot(inner && rin == 0))) >> 1;
+    for (int l = cin + lane; l < ns_small; l += 64) out_small[l] = first;
+}
+
+// the rows of one scale for the two centres of a wave from their ordered lists ord[2][32] (c0, c1 <= 32 entries): slot s of a row
+// is entry s, beyond the list entry 0, of an empty ball 0 (ball_query_gpu.cu:29-43) -- the READING lane pads. NS = 16: both rows
+// in one half wave; otherwise centre 0 in lanes 0-31 and centre 1 in lanes 32-63 (NS = 32: the whole wave stores). NS = 0: run-time ns.
+template <int NS>
+__device__ __forceinline__ void bq_store_rows(int lane, bool two, const int *ord, int c0, int c1, int ns_rt, int *__restrict__ row0,
+                                              int *__restrict__ row1) {
+    const int ns = NS ? NS : ns_rt;
+    if (NS == 16 && lane >= 32) return;
+    const int e = NS == 16 ? lane >> 4 : lane >> 5, s = NS == 16 ? lane & 15 : lane & 31;
+    const int c = e ? c1 : c0;
+    int v = ord[e * 32 + (s < c ? s : 0)];
+    v = c ? v : 0;
+    // (one masked store per row from its scalar base: selecting a 64-bit row address per lane costs more vector instructions)
+    if (e == 0) {
+        if (s < ns) row0[s] = v;
+    } else if (two) {   // an odd tail has no second row
+        if (s < ns) row1[s] = v;
+    }
+    if (NS == 0 && ns > 32 && (e == 0 || two)) {   // (beyond the 32 entries of this path: padding only)
+        int *row = e ? row1 : row0;
+        const int first = c ? ord[e * 32] : 0;
+        for (int l = s + 32; l < ns; l += 32) row[l] = first;
+    }
+}
+
+// ONE emission pass for the two centres of a wave, both lists at or below 32 entries: centre 0's list in lanes 0-31, centre 1's
+// in lanes 32-63; one loop over the entries of the own half (broadcast LDS reads, four entries each) gives every entry its rank
+// among all and among the inner entries of its list; the ordered lists go back through LDS and leave as one store per row.
+// lists: 256 words, 16-byte aligned -- [0, 128) the two lists (64 apart), [128, 256) the ordered copies.
+template <int NSB, int NSS>
+__device__ __forceinline__ void bq_emit_pair(int lane, bool two, int *lists, int c0, int c1, int ns_big, int ns_small,
+                                             int *__restrict__ big0, int *__restrict__ big1, int *__restrict__ small0,
+                                             int *__restrict__ small1) {
+    const int half = lane >> 5, sl = lane & 31;
+    const int c = half ? c1 : c0;
+    int *raw = lists + half * 64;
+    const bool valid = sl < c;
+    __builtin_amdgcn_wave_barrier();
+    int mine = raw[sl];
+    if (!valid) {   // the loop below reads whole groups of four
+        mine = 0x7fffffff;
+        raw[sl] = mine;
+    }
+    __builtin_amdgcn_wave_barrier();
+    int rank = 0, rin = 0;
+    const int nmax = max(c0, c1);
+#pragma unroll 1
+    for (int j = 0; j < nmax; j += 4) {
+        const int4 v = *reinterpret_cast<const int4 *>(raw + j);
+        rank += (v.x < mine ? 1 : 0) + (v.y < mine ? 1 : 0) + (v.z < mine ? 1 : 0) + (v.w < mine ? 1 : 0);
+        rin += (v.x < mine ? v.x & 1 : 0) + (v.y < mine ? v.y & 1 : 0) + (v.z < mine ? v.z & 1 : 0) + (v.w < mine ? v.w & 1 : 0);
+    }
+    const bool inner = valid && (mine & 1);
+    if (valid) lists[128 + half * 32 + rank] = mine >> 1;
+    if (inner) lists[192 + half * 32 + rin] = mine >> 1;
+    const unsigned long long im = __ballot(inner);
+    __builtin_amdgcn_wave_barrier();
+    bq_store_rows<NSB>(lane, two, lists + 128, c0, c1, ns_big, big0, big1);
+    bq_store_rows<NSS>(lane, two, lists + 192, (int)__popc((unsigned)im), (int)__popc((unsigned)(im >> 32)), ns_small, small0, small1);
+}
+
 // 64 < cnt <= 64 * RM hits in `hits`, nsample <= 64: only the nsample SMALLEST original indices are wanted. They are found
 // without a second walk: the indices are distinct integers below np, so count(hits < T) grows by at most one per unit of T and a
 // binary search over T finds the threshold below which exactly nsample of them lie (the lanes hold the list in RM registers; a
@@ -505,6 +595,7 @@ __device__ __forceinline__ void bq_bitmap_search(int lane, int np, float r2, int
     int pos = incl - bc;
     int mine_first = 0x7fffffff;
     if (bc > 0 && (pos < nsample || pos == 0)) {
+#pragma unroll 1   // (unrolled, the (lane * DPL + i) * 32 of every copy of this walk in a kernel stay in registers over its common path)
         for (int i = 0; i < DPL; ++i) {
             unsigned ww = bits[lane * DPL + i];
             if (ww && mine_first == 0x7fffffff) mine_first = (lane * DPL + i) * 32 + (int)__builtin_ctz(ww);
@@ -589,6 +680,25 @@ __global__ __launch_bounds__(kQThreads) void bq_query_kernel(int np, int m, BqSc
     }
 }
 
+// xcd_scene_map in scalar registers, and for a power-of-two grid (every level of the pyramid) without its division: ~25 vector
+// instructions, several of them quarter-rate, at the head of a kernel that is bound by the vector instructions it issues
+__device__ __forceinline__ void xcd_scene_map_uniform(int &wg_x, int &bs) {
+#ifndef EPNET_NO_XCD_MAP
+    const int gx = (int)gridDim.x;
+    if ((gx & (gx - 1)) == 0) {
+        const int nwg = gx * (int)gridDim.y, orig = (int)blockIdx.y * gx + (int)blockIdx.x;
+        const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
+        const int wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
+        bs = wgid >> __builtin_ctz(gx);
+        wg_x = wgid & (gx - 1);
+        return;
+    }
+#endif
+    xcd_scene_map(wg_x, bs);
+    wg_x = __builtin_amdgcn_readfirstlane(wg_x);
+    bs = __builtin_amdgcn_readfirstlane(bs);
+}
+
 // TWO centres per wave. The search is a chain of dependent loads (quad boxes -> bucket boxes -> rows) and the chip
 // holds at most 8 waves per SIMD, so a wave that walks the chain for two centres at once -- quad boxes loaded once
 // and tested against both, the bucket boxes of centre 0 in lanes 0-31 and of centre 1 in lanes 32-63, one candidate
@@ -599,7 +709,12 @@ __global__ __launch_bounds__(kQThreads) void bq_query_kernel(int np, int m, BqSc
 // 4 KB of LDS per wave instead of the N-bit bitmap's 8 KB at 65536 points, which held the kernel at half the waves a CU can
 // keep (the walk is a chain of dependent loads: 0.54 -> 0.32 ms at 32 scenes of BASELINE config 5). The lists are looked at once
 // per step of the walk (<= kRowsPerStep rows = kStepAppends appends per list).
-template <int DPL, int K, bool kStream>
+// K == 2 without kStream: ONE list per centre for both scales (see "shared lists" above): the balls are nested, so a hit is
+// appended once, with a bit for the smaller ball, and the four lists of a wave leave in one emission pass while both centres
+// hold at most 32 hits. A centre above 64 hits takes the bitmap walk for both of its scales (its list has dropped entries the
+// smaller scale may want as well). kStream keeps one list per scale: its cut threshold is per scale. kSpec: nsample = (16, 32)
+// with r2[0] <= r2[1], the pyramid's pair, as compile-time constants.
+template <int DPL, int K, bool kStream, bool kSpec = false>
 __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqScales<K> sc,
                                                               const float *__restrict__ new_xyz,
                                                               const float4 *__restrict__ sorted,
@@ -612,11 +727,13 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
     static_assert(!kStream || CAP - kStepAppends >= 64,
                   "a cut list keeps nsample <= 64 entries (the launcher streams for nsample <= 64 only) and must take a step's appends");
     constexpr int kBitWords = kStream ? 0 : 64 * DPL;
-    __shared__ unsigned s_pool[kQThreads / 64][kBitWords + 2 * K * CAP];   // (the bitmap of a crowded ball,) the hit lists
+    constexpr bool kShared = K == 2 && !kStream;
+    static_assert(!kSpec || kShared, "the compile-time pair is one of the shared-list kernel");
+    __shared__ __attribute__((aligned(16))) unsigned s_pool[kQThreads / 64][kBitWords + 2 * K * CAP];   // (the bitmap of a crowded ball,) the hit lists
     __shared__ int s_quads[kQThreads / 64][2][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int wg_x, bs;
-    xcd_scene_map(wg_x, bs);   // a scene's index passes through one XCD's L2
+    xcd_scene_map_uniform(wg_x, bs);   // a scene's index passes through one XCD's L2
     const int ci0 = (wg_x * (kQThreads / 64) + wave) * 2;
     if (ci0 >= m) return;  // wave-uniform; no block-level barrier below
     const bool two = ci0 + 1 < m;
@@ -637,12 +754,23 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
         ax = c0[0]; ay = c0[1]; az = c0[2];
         bx_ = c1[0]; by_ = c1[1]; bz_ = c1[2];
     }
+    // wave-uniform, but loaded per lane: into scalar registers (the kernel stays at or below 48 VGPRs -- eight waves of it then
+    // leave 128 registers of every SIMD to the sampling chain's kernels it runs beside, which need 126)
+    auto uniform = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    ax = uniform(ax); ay = uniform(ay); az = uniform(az);
+    bx_ = uniform(bx_); by_ = uniform(by_); bz_ = uniform(bz_);
+    out0 = __builtin_amdgcn_readfirstlane(out0);
+    out1 = __builtin_amdgcn_readfirstlane(out1);
     const int half = lane >> 5;  // which centre this lane serves in the bucket-box stage
     const float hx = half ? bx_ : ax, hy = half ? by_ : ay, hz = half ? bz_ : az;
     float r2max = sc.r2[0];
 #pragma unroll
     for (int k = 1; k < K; ++k) r2max = fmaxf(r2max, sc.r2[k]);
-    int cnt[2][K];    // hits so far (kStream: entries in the list)
+    // (kShared) which scale is the larger ball: by r2, whichever order the caller passed (a NaN radius is an empty ball: the smaller)
+    const bool big1 = kSpec || (kShared && (sc.r2[K - 1] >= sc.r2[0] || sc.r2[0] != sc.r2[0]));
+    const float r2small = kShared ? (big1 ? sc.r2[0] : sc.r2[K - 1]) : r2max;
+    if constexpr (kShared) r2max = big1 ? sc.r2[K - 1] : sc.r2[0];
+    int cnt[2][K];    // hits so far (kStream: entries in the list; kShared: [e][0] only)
     int below[2][K];  // (kStream) the list only takes original indices below this
 #pragma unroll
     for (int e = 0; e < 2; ++e)
@@ -665,6 +793,15 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
         const float cx = e ? bx_ : ax, cy = e ? by_ : ay, cz = e ? bz_ : az;
         const float dx = cx - p.x, dy = cy - p.y, dz = cz - p.z;
         const float d2 = dx * dx + dy * dy + dz * dz;
+        if constexpr (kShared) {
+            const bool hit = d2 < r2max;
+            const unsigned long long hm = __ballot(hit);
+            if (!hm) return;
+            const int pos = cnt[e][0] + popc_below(hm);
+            if (hit && pos < 64) hits_of[e * 64 + pos] = (__float_as_int(p.w) << 1) | (d2 < r2small ? 1 : 0);
+            cnt[e][0] += (int)__popcll(hm);
+            return;
+        }
         if (!__ballot(d2 < r2max)) return;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -694,21 +831,28 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
         }
     };
     // one candidate row of each centre per step (both loads in flight together); bucket_of(e, bit)
+    // lane's point of a bucket: the bucket is wave-uniform, so the row's base stays in scalar registers and the lane adds its 16 bytes
+    auto row_of = [&](int bucket) { return (sorted + ((size_t)(unsigned)bucket << 6))[(unsigned)lane]; };
     auto scan_pairs = [&](unsigned long long cand0, unsigned long long cand1, auto &&bucket_of) {
         static_assert(kRowsPerStep == 2, "the step below loads two rows of each centre");
         while (cand0 | cand1) {
             make_room();
-            float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0, p3 = p0;
+            // (no initial values: with a constant on the other edge the compiler folds what visit() first does to a row into the block
+            // of its load, behind a wait for that load alone, and the four rows of a step arrive one after the other)
+            float4 p0, p1, p2, p3;
             const bool h0 = cand0 != 0ull, h1 = cand1 != 0ull;
-            if (h0) { p0 = sorted[(bucket_of(0, (int)__builtin_ctzll(cand0)) << 6) + lane]; cand0 &= cand0 - 1ull; }
-            if (h1) { p1 = sorted[(bucket_of(1, (int)__builtin_ctzll(cand1)) << 6) + lane]; cand1 &= cand1 - 1ull; }
+            if (h0) { p0 = row_of(bucket_of(0, (int)__builtin_ctzll(cand0))); cand0 &= cand0 - 1ull; }
+            if (h1) { p1 = row_of(bucket_of(1, (int)__builtin_ctzll(cand1))); cand1 &= cand1 - 1ull; }
             const bool h2 = cand0 != 0ull, h3 = cand1 != 0ull;
-            if (h2) { p2 = sorted[(bucket_of(0, (int)__builtin_ctzll(cand0)) << 6) + lane]; cand0 &= cand0 - 1ull; }
-            if (h3) { p3 = sorted[(bucket_of(1, (int)__builtin_ctzll(cand1)) << 6) + lane]; cand1 &= cand1 - 1ull; }
+            if (h2) { p2 = row_of(bucket_of(0, (int)__builtin_ctzll(cand0))); cand0 &= cand0 - 1ull; }
+            if (h3) { p3 = row_of(bucket_of(1, (int)__builtin_ctzll(cand1))); cand1 &= cand1 - 1ull; }
             if (h0) visit(0, p0);
             if (h1) visit(1, p1);
             if (h2) visit(0, p2);
             if (h3) visit(1, p3);
+            // every row of the step has arrived by now; saying so (s_waitcnt vmcnt(0)) keeps the compiler from assuming, on the way
+            // round the loop, a load still in flight into p0 .. p3 and waiting before it reuses their registers for the next addresses
+            __builtin_amdgcn_s_waitcnt(0x0F70);
         }
     };
     if constexpr (DPL <= 2) {  // <= 64 buckets: every bucket box once, tested against both centres
@@ -722,12 +866,11 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
         const int nq = np >> 8;
         for (int q0 = 0; q0 < nq; q0 += 64) {
             const int qd = q0 + lane;
-            bool n0 = false, n1 = false;
-            if (qd < nq) {
-                n0 = box_near(qboxes + qd * 6, ax, ay, az, r2max);
-                n1 = box_near(qboxes + qd * 6, bx_, by_, bz_, r2max);
-            }
-            const unsigned long long qm0 = __ballot(n0), qm1 = __ballot(n1);
+            // (a lane past the last quad tests the last one again and drops the answer: no branch around the loads, and the ballots
+            // come straight from the compares; 24-bit multiplies: full rate)
+            const float *qb = qboxes + __umul24(min(qd, nq - 1), 6);
+            const bool n0 = box_near(qb, ax, ay, az, r2max) && qd < nq, n1 = box_near(qb, bx_, by_, bz_, r2max) && qd < nq;
+            const unsigned long long qm0 = __builtin_amdgcn_ballot_w64(n0), qm1 = __builtin_amdgcn_ballot_w64(n1);   // (of a bool: no 0 / 1 round trip)
             if (!(qm0 | qm1)) continue;
             const int nq0 = (int)__popcll(qm0), nq1 = (int)__popcll(qm1);
             if (n0) s_quads[wave][0][popc_below(qm0)] = qd;
@@ -740,9 +883,9 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
                 bool bnear = false;
                 if (slot < nmine) {
                     bid = s_quads[wave][half][slot] * 4 + (lane & 3);
-                    bnear = box_near(boxes + bid * 6, hx, hy, hz, r2max);
+                    bnear = box_near(boxes + __umul24(bid, 6), hx, hy, hz, r2max);
                 }
-                const unsigned long long cand = __ballot(bnear);
+                const unsigned long long cand = __builtin_amdgcn_ballot_w64(bnear);
                 scan_pairs(cand & 0xFFFFFFFFull, cand >> 32,
                            [&](int e, int bit) { return __builtin_amdgcn_readlane(bid, bit + 32 * e); });
             }
@@ -752,32 +895,62 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
 #ifdef EPNET_BQ_STATS
     const unsigned long long st_1 = __builtin_amdgcn_s_memtime();
 #endif
+    if constexpr (kShared) {
+        const int ns0 = kSpec ? 16 : sc.nsample[0], ns1 = kSpec ? 32 : sc.nsample[K - 1];
+        const int ns_big = big1 ? ns1 : ns0, ns_small = big1 ? ns0 : ns1;
+        int *idx_big = big1 ? sc.idx[K - 1] : sc.idx[0], *idx_small = big1 ? sc.idx[0] : sc.idx[K - 1];
+        const size_t row0 = (size_t)bs * m + out0, row1 = (size_t)bs * m + out1;
+        const int c0 = cnt[0][0], c1 = cnt[1][0];
+        if (c0 <= 32 && c1 <= 32) {   // (wave-uniform) the common path; an odd tail walked centre 0 twice and stores one row
+            bq_emit_pair<kSpec ? 32 : 0, kSpec ? 16 : 0>(lane, two, hits_of, c0, c1, ns_big, ns_small, idx_big + row0 * ns_big,
+                                                         idx_big + row1 * ns_big, idx_small + row0 * ns_small, idx_small + row1 * ns_small);
+        } else {
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        if (e == 1 && !two) break;
-        const float cx = e ? bx_ : ax, cy = e ? by_ : ay, cz = e ? bz_ : az;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            int *out = sc.idx[k] + ((size_t)bs * m + (e ? out1 : out0)) * sc.nsample[k];
-            int *hits = hits_of + (e * K + k) * CAP;
-            if constexpr (kStream) {
-                if (cnt[e][k] > 64) {   // (a list that was cut before holds nsample or more candidates: the same selection)
-                    bq_select_smallest<CAP / 64>(lane, hits, cnt[e][k], sc.nsample[k], np);
-                    cnt[e][k] = sc.nsample[k];
-#ifdef EPNET_BQ_STATS
-                    st_sel = true;
-#endif
-                }
-                bq_emit_list(lane, hits, cnt[e][k], sc.nsample[k], out);
-            } else {
-                if (cnt[e][k] <= 64) {
-                    bq_emit_list(lane, hits, cnt[e][k], sc.nsample[k], out);
+            for (int e = 0; e < 2; ++e) {
+                if (e == 1 && !two) break;
+                const size_t row = e ? row1 : row0;
+                if (cnt[e][0] <= 64) {
+                    bq_emit_shared(lane, hits_of + e * 64, cnt[e][0], ns_big, ns_small, idx_big + row * ns_big, idx_small + row * ns_small);
                 } else {
 #ifdef EPNET_BQ_STATS
                     st_again = true;
 #endif
-                    bq_bitmap_search<DPL>(lane, np, sc.r2[k], sc.nsample[k], cx, cy, cz, sorted, boxes, qboxes, out, s_pool[wave],
+                    const float cx = e ? bx_ : ax, cy = e ? by_ : ay, cz = e ? bz_ : az;
+                    bq_bitmap_search<DPL>(lane, np, r2max, ns_big, cx, cy, cz, sorted, boxes, qboxes, idx_big + row * ns_big, s_pool[wave],
                                           s_quads[wave][0]);
+                    bq_bitmap_search<DPL>(lane, np, r2small, ns_small, cx, cy, cz, sorted, boxes, qboxes, idx_small + row * ns_small,
+                                          s_pool[wave], s_quads[wave][0]);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (e == 1 && !two) break;
+            const float cx = e ? bx_ : ax, cy = e ? by_ : ay, cz = e ? bz_ : az;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                int *out = sc.idx[k] + ((size_t)bs * m + (e ? out1 : out0)) * sc.nsample[k];
+                int *hits = hits_of + (e * K + k) * CAP;
+                if constexpr (kStream) {
+                    if (cnt[e][k] > 64) {   // (a list that was cut before holds nsample or more candidates: the same selection)
+                        bq_select_smallest<CAP / 64>(lane, hits, cnt[e][k], sc.nsample[k], np);
+                        cnt[e][k] = sc.nsample[k];
+#ifdef EPNET_BQ_STATS
+                        st_sel = true;
+#endif
+                    }
+                    bq_emit_list(lane, hits, cnt[e][k], sc.nsample[k], out);
+                } else {
+                    if (cnt[e][k] <= 64) {
+                        bq_emit_list(lane, hits, cnt[e][k], sc.nsample[k], out);
+                    } else {
+#ifdef EPNET_BQ_STATS
+                        st_again = true;
+#endif
+                        bq_bitmap_search<DPL>(lane, np, sc.r2[k], sc.nsample[k], cx, cy, cz, sorted, boxes, qboxes, out, s_pool[wave],
+                                              s_quads[wave][0]);
+                    }
                 }
             }
         }
@@ -857,11 +1030,16 @@ static int bq_query_launch(int b, int np, int m, const BqScales<K> &sc, const fl
         const int stream_force = tuning(kBqStream);
         bool stream = stream_force >= 0 ? stream_force != 0 : np > 16384;
         for (int k = 0; k < K; ++k) stream = stream && sc.nsample[k] <= 64;
+        // the pyramid's pair of scales with its sample counts as compile-time constants (see the kernel)
+        const bool spec = K == 2 && !stream && sc.nsample[0] == 16 && sc.nsample[K - 1] == 32 && sc.r2[0] <= sc.r2[K - 1];
 #define EPNET_BQ2(D_)                                                                                                                   \
     do {                                                                                                                                \
         if (stream)                                                                                                                     \
             hipLaunchKernelGGL((bq_query2_kernel<D_, K, true>), grid, dim3(kQThreads), 0, s, np, m, sc, new_xyz, sorted, boxes, qboxes,   \
                                order, npc);                                                                                             \
+        else if (spec)                                                                                                                  \
+            hipLaunchKernelGGL((bq_query2_kernel<D_, K, false, K == 2>), grid, dim3(kQThreads), 0, s, np, m, sc, new_xyz, sorted, boxes, \
+                               qboxes, order, npc);                                                                                     \
         else                                                                                                                            \
             hipLaunchKernelGGL((bq_query2_kernel<D_, K, false>), grid, dim3(kQThreads), 0, s, np, m, sc, new_xyz, sorted, boxes,         \
                                qboxes, order, npc);                                                                                     \
