@@ -271,11 +271,54 @@ def targets_rows(args, report, timeit_pair):
                % (nbytes / (ms_f * 1e-3) / peak, ms_l, chunk[0], ms_c, ms_c2, agree))
 
 
+def rcnn_targets_rows(args, report, timeit_pair):
+    """the sync-free RCNN target layer (epnet_amd/rcnn_target_layer.py: epnet_rcnn_sample_rois + epnet_roipool3d_train, device
+    tables) against the existing ProposalTargetLayer (host random streams, two read-backs), alternating inside one call, at
+    1 / 2 / 16 scenes x 512 ROIs x 20 box rows (12 real) x 16384 points x 130 feature columns, R = 64, S = 512; then the two
+    calls of the new layer on their own"""
+    import torch
+    from epnet_amd import proposal_target_layer as ptl, rcnn_target_layer as rtl, synth
+    dev = torch.device("cuda:0")
+    m, n, g_rows, r, s_num, c = 512, 16384, 20, 64, 512, 130
+    g = torch.Generator().manual_seed(0)
+    for bsz in (1, 2, 16):
+        rl, gl = [], []
+        for i in range(bsz):
+            bx, _ = synth.proposal_boxes(m + 12, seed=200 + i, num_objects=12, jitter=0.4)
+            gt = torch.zeros((g_rows, 7)); gt[:12] = bx[m:]
+            rl.append(bx[:m]); gl.append(gt)
+        layer_in = {"roi_boxes3d": torch.stack(rl).to(dev), "gt_boxes3d": torch.stack(gl).to(dev),
+                    "rpn_xyz": synth.scenes("kitti", bsz, n, seed=9).to(dev), "rpn_features": torch.randn((bsz, n, c - 2), generator=g).to(dev),
+                    "seg_mask": (torch.rand((bsz, n), generator=g) > 0.5).float().to(dev), "pts_depth": (torch.rand((bsz, n), generator=g) * 70).to(dev)}
+        host_layer, fused_layer = ptl.ProposalTargetLayer(), rtl.RCNNTargetLayer()
+        cfg = fused_layer.cfg
+        ms_host, ms_fused = timeit_pair(lambda: host_layer(layer_in), lambda: fused_layer(layer_in))
+        tables = rtl.draw_sampling_tables(bsz, m, cfg, dev)
+        feat = torch.cat([layer_in["seg_mask"].unsqueeze(2), (layer_in["pts_depth"] / 70.0 - 0.5).unsqueeze(2), layer_in["rpn_features"]], dim=2)
+        sampled = rtl.sample_rois(layer_in["roi_boxes3d"], layer_in["gt_boxes3d"], tables, cfg)
+        ms_draw, ms_sample = timeit_pair(lambda: rtl.draw_sampling_tables(bsz, m, cfg, dev),
+                                         lambda: rtl.sample_rois(layer_in["roi_boxes3d"], layer_in["gt_boxes3d"], tables, cfg))
+        ms_cat, ms_pool = timeit_pair(lambda: torch.cat([layer_in["seg_mask"].unsqueeze(2), (layer_in["pts_depth"] / 70.0 - 0.5).unsqueeze(2),
+                                                         layer_in["rpn_features"]], dim=2),
+                                      lambda: rtl.pool_targets(layer_in["rpn_xyz"], feat, sampled[0], sampled[1], sampled[2], tables["aug"], cfg))
+        info = sampled[3].tolist()
+        sample_bytes = bsz * (m * 28 + g_rows * 7 * 4 + m * 4 + r * 4) + bsz * r * (28 + 28 + 4) + bsz * 24
+        pool_bytes = bsz * (n * 12 + n * c * 4 + r * (28 * 2 + 4 + 12) + r * s_num * (3 + c) * 4 + r * (28 * 2 + 16))
+        report("RCNNTargetLayer.forward", {"B": bsz, "proposals": m, "G": g_rows, "rois": r, "N": n, "C": c, "S": s_num,
+                                           "fg_num": [row[1] for row in info]}, ms_fused, pool_bytes + sample_bytes,
+               "device tables + epnet_rcnn_sample_rois + feature cat + epnet_roipool3d_train, no host sync; the existing ProposalTargetLayer "
+               "(host random streams, two read-backs) in the same pair: %.4f ms; on their own: table draws %.4f ms, sample_rois %.4f ms "
+               "(%d bytes of inputs, tables and outputs, noise tables and the IoU matrix aside), feature cat %.4f ms, pool_targets %.4f ms"
+               % (ms_host, ms_draw, ms_sample, sample_bytes, ms_cat, ms_pool))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--loss-only", action="store_true", help="only the training-loss rows (fused against the two stock-torch forms)")
     ap.add_argument("--targets-only", action="store_true", help="only the RPN training targets (fused against bench_step.rpn_labels)")
+    ap.add_argument("--rcnn-targets-only", action="store_true",
+                    help="only the RCNN training targets (the sync-free RCNNTargetLayer against the existing ProposalTargetLayer)")
     ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
     args = ap.parse_args()
     import torch
@@ -391,6 +434,8 @@ def main():
         return loss_rows(args, report, timeit_pair)
     if args.targets_only:
         return targets_rows(args, report, timeit_pair)
+    if args.rcnn_targets_only:
+        return rcnn_targets_rows(args, report, timeit_pair)
     # ---- NMS at the proposal-layer sizes (RPN.NMS_TYPE normal, N <= 6300 / 2700, thresh 0.85) and eval rotated NMS
     for n, rot, thr in ((6300, False, 0.85), (2700, False, 0.85), (6300, True, 0.8), (512, True, 0.1), (100, True, 0.1)):
         boxes, scores = synth.proposal_boxes(n, seed=n, num_objects=40, jitter=1.5)

@@ -12,7 +12,8 @@ What is timed (forward + backward + SGD step, `--batch` scenes per GPU):
   RPN backbone   4 SA-MSG levels 16384>4096>1024>256>64 + 4 FP levels (lib/net/pointnet2_msg.py:126-196, point stream) and
                  the cls / reg heads (lib/net/rpn.py:23-52)
   proposals      ProposalLayer (decode, distance-based NMS, 512 proposals per scene)
-  targets        ProposalTargetLayer (IoU, ROI sampling + augmentation, roipool3d 64 x 512 x 133, canonical transform)
+  targets        ProposalTargetLayer (IoU, ROI sampling + augmentation, roipool3d 64 x 512 x 133, canonical transform);
+                 --targets fused: the sync-free RCNNTargetLayer (epnet_rcnn_sample_rois + epnet_roipool3d_train)
   RCNN stage     3 SA levels over 64 ROIs x 512 points per scene (128 > 32 > group-all) and two FC heads
                  (lib/net/rcnn_net.py:43-93, without its loss bookkeeping)
 Every geometry op is this package's HIP path; every dense layer (shared MLPs, batch norm, image convolutions, attention
@@ -282,6 +283,9 @@ def main():
                     help="the step's loss: sums of squares (default), the real RPN + RCNN losses fused (epnet_amd.loss_utils), or the "
                          "real losses composed from stock torch calls as the reference does, mask indexing and .item() reads included; "
                          "the RPN labels are built on the device outside the timed region")
+    ap.add_argument("--targets", default="host", choices=["host", "fused"],
+                    help="the RCNN target layer: the draw-for-draw restatement of the reference's host random streams (two read-backs "
+                         "per step, default) or the sync-free epnet_amd.rcnn_target_layer.RCNNTargetLayer (device tables, two calls)")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without a torch.distributed.run environment the ranks are started as child processes")
     ap.add_argument("--launch-check", action="store_true", help="rehearse the N-rank launch only (see bench.py)")
@@ -324,7 +328,11 @@ def main():
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local], find_unused_parameters=False)
     opt = torch.optim.SGD(model.parameters(), lr=1e-4, momentum=0.9)
-    layers = (pl.ProposalLayer("TRAIN").to(device), ptl.ProposalTargetLayer())
+    if args.targets == "fused":
+        from epnet_amd import rcnn_target_layer as rtl
+        layers = (pl.ProposalLayer("TRAIN").to(device), rtl.RCNNTargetLayer())
+    else:
+        layers = (pl.ProposalLayer("TRAIN").to(device), ptl.ProposalTargetLayer())
     xyz, gts = synthetic_batch(args.batch, args.points, 100 + 1000 * rank, device)   # every rank its own scenes
     image = xy = None
     if args.image:
@@ -414,9 +422,9 @@ def main():
     import bench
     from epnet_amd import iou3d_cuda, pointnet2_cuda, roipool3d_cuda
     iou_names = [n for n in ("boxes_overlap_bev_gpu", "boxes_iou_bev_gpu", "boxes_iou3d_fused_gpu", "boxes_iou3d_pairs_gpu",
-                             "aug_roi_by_noise_gpu", "rpn_proposals_gpu", "nms_device", "nms_normal_device")]
+                             "aug_roi_by_noise_gpu", "rpn_proposals_gpu", "nms_device", "nms_normal_device", "rcnn_sample_rois_gpu")]
     timers = ([bench.OpTimer(torch, pointnet2_cuda), bench.OpTimer(torch, iou3d_cuda, iou_names),
-               bench.OpTimer(torch, roipool3d_cuda, ["forward"])] if rank == 0 else [])
+               bench.OpTimer(torch, roipool3d_cuda, ["forward", "forward_train"])] if rank == 0 else [])
     reps = max(2, min(5, args.steps))
     with contextlib.ExitStack() as stack:       # (every rank takes the steps: the gradient all-reduce needs all of them)
         for t in timers:
@@ -447,7 +455,7 @@ def main():
                 "RPN fwd+bwd, point stream only" if args.rpn_only else
                 "rcnn_online point-stream training step (BASELINE config 4 without the image stream)")
         print(json.dumps({"metric": what, "n_gpus": world, "image_stream": bool(args.image), "rpn_only": bool(args.rpn_only),
-                          "sampler": args.sampler, "ops_share": ops_share,
+                          "sampler": args.sampler, "targets": args.targets, "ops_share": ops_share,
                           "scenes_per_gpu": args.batch, "points_per_scene": args.points, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(elapsed / args.steps * 1e3, 3),
                           "ms_per_step_median": round(sorted(per_step)[len(per_step) // 2] * 1e3, 3),
@@ -463,7 +471,9 @@ def main():
                           "loss": last, "data": "synthetic", "dtype": "f32",
                           **({} if args.loss == "placeholder" else {"loss_mode": args.loss, "loss_terms": {
                               n_: round(float(v), 6) for r_ in last_out.values() for n_, v in zip(r_.names, r_.terms.tolist())}}),
-                          "note": "phase_ms from HIP events (phases are host-serialised by the two syncs of the target layer); "
+                          "note": "phase_ms from HIP events (%s); "
+                                  % ("phases are host-serialised by the two syncs of the target layer" if args.targets == "host" else
+                                     "the target layer does not synchronise with the host") +
                                   "dense layers are stock PyTorch-ROCm, geometry ops this package's HIP kernels"}))
     if world > 1:
         dist.destroy_process_group()

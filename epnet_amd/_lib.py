@@ -82,6 +82,9 @@ SIGNATURES = {
     "epnet_boxes_iou3d": (_i, [_i, _vp, _i, _vp, _vp, _vp]),
     "epnet_boxes_iou3d_pairs": (_i, [_i, _vp, _vp, _vp, _vp]),
     "epnet_aug_roi_by_noise": (_i, [_i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_rcnn_sample_rois_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "epnet_rcnn_sample_rois": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, _f, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_rpn_proposals_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "epnet_rpn_proposals": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "epnet_rcnn_detections_workspace_bytes": (_sz, [_i, _i]),
@@ -92,6 +95,8 @@ SIGNATURES = {
     "epnet_roipool3d_workspace_bytes": (_sz, [_i, _i, _i]),
     "epnet_roipool3d": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "epnet_roipool3d_canonical": (_i, [_i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_roipool3d_train": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp]),
     "epnet_box_loss_workspace_bytes": (_sz, [ctypes.c_longlong, _i]),
     "epnet_box_loss": (_i, [ctypes.c_longlong, _i, _d, _d, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

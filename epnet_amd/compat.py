@@ -68,14 +68,22 @@ def install_surface(include_kitti_utils=False):
         setattr(sys.modules[parent], leaf, mod)
 
 
-def install_callers():
+def install_callers(sync_free=False):
     """serve this package's ProposalLayer / ProposalTargetLayer under the reference's module paths, so that
     lib/net/rpn.py and lib/net/rcnn_net.py construct them unchanged; both read the reference's ``lib.config.cfg`` when
-    that module is loaded (same attribute names), their own yaml-valued defaults otherwise"""
+    that module is loaded (same attribute names), their own yaml-valued defaults otherwise. The default target layer is the
+    draw-for-draw restatement of the reference's host random streams; sync_free=True serves
+    ``rcnn_target_layer.RCNNTargetLayer`` (same distributions, device tables, no host synchronisation) under the reference's
+    class name instead"""
     install_extensions()
     for dotted, local in _CALLERS.items():
         _ensure_package(dotted)
         mod = importlib.import_module("epnet_amd." + local)
+        if sync_free and local == "proposal_target_layer":
+            fused = importlib.import_module("epnet_amd.rcnn_target_layer")
+            mod = types.ModuleType(dotted)
+            mod.__dict__.update({k: v for k, v in vars(fused).items() if not k.startswith("__")})
+            mod.ProposalTargetLayer = fused.RCNNTargetLayer
         sys.modules[dotted] = mod
         parent, leaf = dotted.rsplit(".", 1)
         setattr(sys.modules[parent], leaf, mod)

@@ -79,6 +79,69 @@ def aug_roi_by_noise_gpu(roi_boxes3d, gt_boxes3d, iou3d_src, keep_draw, noise, p
     return 1
 
 
+def _overlap(a, b):
+    """do the bytes of two tensors intersect"""
+    if a.numel() == 0 or b.numel() == 0 or a.device != b.device:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+@writes("batch_rois", "batch_gt_of_rois", "batch_roi_iou", "scene_info", "src_inds", "iou_src", "tries", "max_overlaps", "gt_assignment")
+def rcnn_sample_rois_gpu(rois, gt_boxes3d, fg_key, slot_u, keep_draw, noise, fg_per_image, fg_thresh, cls_bg_thresh, cls_bg_thresh_lo,
+                         hard_bg_ratio, batch_rois, batch_gt_of_rois, batch_roi_iou, scene_info, src_inds=None, iou_src=None, tries=None,
+                         max_overlaps=None, gt_assignment=None):
+    """lib/rpn/proposal_target_layer.py:85-218 (sample_rois_for_rcnn) for the whole batch, no host sync: rois (B,M,7),
+    gt_boxes3d (B,G,gc) zero-padded, the draw tables fg_key (B,M) and slot_u (B,R), keep_draw (B*R,T) uint8 and noise (B*R,T,7)
+    (both None for no noise loop) -> batch_rois (B,R,7), batch_gt_of_rois (B,R,7), batch_roi_iou (B,R), scene_info (B,6) int32
+    and, where given, src_inds / tries (B,R) int32, iou_src (B,R), max_overlaps (B,M), gt_assignment (B,M) int32 (not in the
+    reference extension; see epnet_ops.h)"""
+    if rois.dim() != 3 or rois.shape[2] != 7:
+        raise RuntimeError("rois must be (B, M, 7)")
+    if gt_boxes3d.dim() != 3 or gt_boxes3d.shape[0] != rois.shape[0]:
+        raise RuntimeError("gt_boxes3d must be (B, G, 7..16)")
+    if fg_key.dim() != 2 or tuple(fg_key.shape) != (rois.shape[0], rois.shape[1]):
+        raise RuntimeError("fg_key must be (B, M)")
+    if slot_u.dim() != 2 or slot_u.shape[0] != rois.shape[0]:
+        raise RuntimeError("slot_u must be (B, R)")
+    b, m, g, gc, r = rois.shape[0], rois.shape[1], gt_boxes3d.shape[1], gt_boxes3d.shape[2], slot_u.shape[1]
+    t = keep_draw.size(1) if keep_draw is not None else 0
+    I = torch.int32
+    pr, pg = dev_ptr(rois, "rois", _F), dev_ptr(gt_boxes3d, "gt_boxes3d", _F)
+    pk, pu = dev_ptr(fg_key, "fg_key", _F), dev_ptr(slot_u, "slot_u", _F)
+    need(fg_key, b * m, "fg_key"); need(slot_u, b * r, "slot_u")
+    outs = [dev_ptr(batch_rois, "batch_rois", _F), dev_ptr(batch_gt_of_rois, "batch_gt_of_rois", _F),
+            dev_ptr(batch_roi_iou, "batch_roi_iou", _F), dev_ptr(scene_info, "scene_info", I)]
+    need(batch_rois, b * r * 7, "batch_rois"); need(batch_gt_of_rois, b * r * 7, "batch_gt_of_rois")
+    need(batch_roi_iou, b * r, "batch_roi_iou"); need(scene_info, b * 6, "scene_info")
+    for name, out, dtype, count in (("src_inds", src_inds, I, b * r), ("iou_src", iou_src, _F, b * r), ("tries", tries, I, b * r),
+                                    ("max_overlaps", max_overlaps, _F, b * m), ("gt_assignment", gt_assignment, I, b * m)):
+        if out is None:
+            outs.append(None)
+        else:
+            outs.append(dev_ptr(out, name, dtype))
+            need(out, count, name)
+    pd = pn = None
+    if t:
+        pd, pn = dev_ptr(keep_draw, "keep_draw", torch.uint8), dev_ptr(noise, "noise", _F)
+        need(keep_draw, b * r * t, "keep_draw"); need(noise, b * r * t * 7, "noise")
+    # no output may alias an input (the selection reads whole scenes of every input while other slots are being written)
+    given = (batch_rois, batch_gt_of_rois, batch_roi_iou, scene_info, src_inds, iou_src, tries, max_overlaps, gt_assignment)
+    for out in given:
+        for name, inp in (("rois", rois), ("gt_boxes3d", gt_boxes3d), ("fg_key", fg_key), ("slot_u", slot_u), ("keep_draw", keep_draw),
+                          ("noise", noise)):
+            if out is not None and inp is not None and _overlap(out, inp):
+                raise RuntimeError("an output must not alias %s" % name)
+    l = _lib.lib()
+    ws_bytes = l.epnet_rcnn_sample_rois_workspace_bytes(b, m, g, r)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=rois.device)
+    with on_device_of(rois) as s:
+        _lib.check(l.epnet_rcnn_sample_rois(b, m, g, gc, r, int(fg_per_image), float(fg_thresh), float(cls_bg_thresh),
+                                            float(cls_bg_thresh_lo), float(hard_bg_ratio), t, pr, pg, pk, pu, pd, pn, ws.data_ptr(),
+                                            ws.numel(), *outs, s), "rcnn_sample_rois")
+    return 1
+
+
 @writes("ret_bbox3d", "ret_scores", "ret_count")
 def rpn_proposals_gpu(proposals, scores, order, distance_based, pre_nms_top_n, post_nms_top_n, nms_thresh, rotated,
                       ret_bbox3d, ret_scores, ret_count=None):

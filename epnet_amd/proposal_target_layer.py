@@ -66,10 +66,18 @@ def aug_tables_from_raw(coin, which, u, method="multiple"):
         hwl_scale = (u[..., 3:6] - 0.5) / (0.5 / 0.15) + 1.0
         angle_rot = (u[..., 6:7] - 0.5) / (0.5 / (np.pi / 12))
     elif method == "multiple":    # :261-275
-        rng = torch.tensor(_RANGE_CONFIG, dtype=torch.float32, device=u.device)[which]        # (K,T,3)
-        pos_shift = ((u[..., 0:3] - 0.5) / 0.5) * rng[..., 0:1]
-        hwl_scale = ((u[..., 3:6] - 0.5) / 0.5) * rng[..., 1:2] + 1.0
-        angle_rot = ((u[..., 6:7] - 0.5) / 0.5) * rng[..., 2:3]
+        # range_config[which] (K,T) per column, selected with the rows as scalars: a table tensor would have to come from the
+        # host (torch.tensor(..., device=...) is a blocking copy that a stream capture refuses); same fp32 values
+        picks = [which == k for k in range(1, len(_RANGE_CONFIG))]
+        rng = []
+        for col in range(3):
+            sel = torch.where(picks[0], _RANGE_CONFIG[1][col], _RANGE_CONFIG[0][col])
+            for k in range(2, len(_RANGE_CONFIG)):
+                sel = torch.where(picks[k - 1], _RANGE_CONFIG[k][col], sel)
+            rng.append(sel.to(torch.float32).unsqueeze(-1))
+        pos_shift = ((u[..., 0:3] - 0.5) / 0.5) * rng[0]
+        hwl_scale = ((u[..., 3:6] - 0.5) / 0.5) * rng[1] + 1.0
+        angle_rot = ((u[..., 6:7] - 0.5) / 0.5) * rng[2]
     else:
         # 'normal' (:276-289) ADDS gaussian noise to h, w, l and cannot run in the reference either (`torch.rand()`
         # without a size, :283)

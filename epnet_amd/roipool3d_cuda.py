@@ -37,6 +37,38 @@ def forward_canonical(xyz, rois, pts_feature, pool_extra_width, pooled_features,
     return 1
 
 
+@writes("sampled_pts", "pts_feature_out", "rois_out", "gt_out", "cls_label", "reg_valid_mask", "mask_score", "pooled_empty_flag")
+def forward_train(xyz, pts_feature, rois, gt_of_rois, roi_iou, aug, pool_extra_width, reg_fg_thresh, cls_fg_thresh, cls_bg_thresh,
+                  sampled_pts, pts_feature_out, rois_out, gt_out, cls_label, reg_valid_mask, mask_score, pooled_empty_flag):
+    """the tail of ProposalTargetLayer.forward (lib/rpn/proposal_target_layer.py:16-83) in one launch: pooling on the enlarged
+    ROIs, per-ROI data augmentation (aug (B,R,3) = [angle, scale, flip] or None), canonical transformation and labels; every
+    element of every output is written (not in the reference extension; see epnet_ops.h)"""
+    I = torch.int32
+    px, pf, pb = dev_ptr(xyz, "xyz", _F), dev_ptr(pts_feature, "pts_feature", _F), dev_ptr(rois, "rois", _F)
+    pg, pi = dev_ptr(gt_of_rois, "gt_of_rois", _F), dev_ptr(roi_iou, "roi_iou", _F)
+    b, n = xyz.size(0), xyz.size(1)
+    m, c, s_num = rois.size(1), pts_feature.size(2), sampled_pts.size(1)
+    need(xyz, b * n * 3, "xyz"); need(rois, b * m * 7, "rois"); need(pts_feature, b * n * c, "pts_feature")
+    need(gt_of_rois, b * m * 7, "gt_of_rois"); need(roi_iou, b * m, "roi_iou")
+    pa = None
+    if aug is not None:
+        pa = dev_ptr(aug, "aug", _F)
+        need(aug, b * m * 3, "aug")
+    outs = []
+    for name, out, dtype, count in (("sampled_pts", sampled_pts, _F, b * m * s_num * 3), ("pts_feature_out", pts_feature_out, _F, b * m * s_num * c),
+                                    ("rois_out", rois_out, _F, b * m * 7), ("gt_out", gt_out, _F, b * m * 7), ("cls_label", cls_label, I, b * m),
+                                    ("reg_valid_mask", reg_valid_mask, I, b * m), ("mask_score", mask_score, _F, b * m),
+                                    ("pooled_empty_flag", pooled_empty_flag, I, b * m)):
+        outs.append(dev_ptr(out, name, dtype))
+        need(out, count, name)
+    if b * m and (outs[2] == pb or outs[3] == pg):
+        raise RuntimeError("rois_out / gt_out must not alias rois / gt_of_rois")
+    with on_device_of(xyz) as s:
+        _lib.check(_lib.lib().epnet_roipool3d_train(b, n, m, c, s_num, float(pool_extra_width), float(reg_fg_thresh), float(cls_fg_thresh),
+                                                    float(cls_bg_thresh), px, pf, pb, pg, pi, pa, *outs, s), "roipool3d_train")
+    return 1
+
+
 # forward_slow (roipool3d.cpp:15-44) computes the same result with one thread per box; same entry here
 forward_slow = forward
 

@@ -361,6 +361,48 @@ int epnet_aug_roi_by_noise(int k, int aug_times, float pos_thresh, float *roi_bo
                            const float *iou3d_src, const int *tries, const unsigned char *keep_draw,
                            const float *noise, float *iou_of_rois, epnet_stream_t stream);
 
+/* sample_rois_for_rcnn, lib/rpn/proposal_target_layer.py:85-218, for all b scenes in one call with no host synchronisation
+ * and no allocation (the reference reads three `nonzero` results per scene and draws on the host). rois (b,m,7); gt_boxes3d
+ * (b,g,gc), 7 <= gc <= 16, zero-padded as collate_batch pads; the caller's draw tables fg_key (b,m) and slot_u (b,r), uniform
+ * in [0,1); keep_draw (b*r,t) u8 and noise (b*r,t,7) as epnet_aug_roi_by_noise takes them (NULL allowed when aug_times t == 0);
+ * r = ROI_PER_IMAGE. Per scene, in this order:
+ *   padding (:105-108): num_gt = 1 + the last row whose fp32 sum over all gc columns, taken in ascending column order, is not
+ *     0; zero rows in front of it stay (boxes with IoU 0). A scene WITHOUT such a row (the reference indexes below 0 there) is
+ *     treated as num_gt = 1 with the zero row 0: every IoU is 0, every ROI easy background; scene_info reports num_gt 0.
+ *   assignment: max_overlaps[i] = max over j < num_gt of the 3-D IoU of (roi_i, gt_j), bit for bit epnet_boxes_iou3d's value;
+ *     gt_assignment[i] = the FIRST j that reaches it (a NaN IoU wins over every number; the first one stays).
+ *   classes, each list in ascending ROI index (torch.nonzero): fg ov >= fg_thresh; easy ov < cls_bg_thresh_lo; hard
+ *     ov < cls_bg_thresh && ov >= cls_bg_thresh_lo. A NaN maximum is in no list.
+ *   selection (:129-156, :191-218) with pick(list, u) = list[min((int)(u * (float)len), len - 1)], one fp32 multiply, entry 0
+ *     for a NaN or negative u:
+ *     case 0, fg and bg present: fg_this = min(fg_per_image, fg_num); slots 0..fg_this-1 are the fg_this foreground candidates
+ *       with the smallest fg_key in ascending key order, ties by ascending ROI index (keys compared as floats, -0 == +0, every
+ *       NaN above +inf): a uniform subset without replacement in uniform order, np.random.permutation's distribution. Slots
+ *       j >= fg_this use slot_u[j]: with hard and easy both present the first (int)((r - fg_this) * hard_bg_ratio) of them
+ *       (a double product, as Python's) pick from hard and the rest from easy; with one kind present all pick from it.
+ *     case 1, fg only: every slot is pick(fg, slot_u[j]), fg_this = r.    case 2, bg only: fg_this = 0, the background rule
+ *       over all r slots.    case 3, neither (the reference stops in pdb): slot j takes ROI min((int)(slot_u[j] * m), m - 1),
+ *       fg_this = 0 (such rows have an IoU between the thresholds: class -1 and no regression later).
+ *   gather: batch_rois = rois[src], batch_gt_of_rois = columns 0..6 of gt[gt_assignment[src]], iou_src = max_overlaps[src];
+ *     tries = aug_times for the slots below fg_this, (aug_times > 0 ? 1 : 0) for the others (:164-176).
+ *   noise loop (:158-179): with aug_times > 0, epnet_aug_roi_by_noise's kernels over all b * r rows with pos_thresh =
+ *     fg_thresh update batch_rois in place and write batch_roi_iou; with aug_times == 0 batch_roi_iou = iou_src.
+ * Results: batch_rois (b,r,7), batch_gt_of_rois (b,r,7), batch_roi_iou (b,r), scene_info (b,6) i32 = [num_gt as counted (0 if
+ * none), fg_num, hard_num, easy_num, fg_this, case]; optional (NULL allowed) src_inds (b,r) i32, iou_src (b,r), tries (b,r)
+ * i32, max_overlaps (b,m), gt_assignment (b,m) i32. Every element of every given output is written; no float atomics: the bits
+ * depend on the inputs alone. Limits, checked before any launch: 1 <= m <= 4096, 1 <= r <= 1024, g >= 1, b <= 65535, else
+ * EPNET_ELIMIT; a NULL required pointer, gc out of range or fg_per_image > r: EPNET_EINVAL; a workspace below
+ * epnet_rcnn_sample_rois_workspace_bytes(b, m, g, r) (pure arithmetic: num_gt, the (b,m,g) IoU matrix, maxima, assignment,
+ * tries, iou_src, each rounded up to 16 bytes; 0 outside the limits): EPNET_ENOMEM; b == 0 returns EPNET_OK and writes nothing.
+ * PRECONDITION: no output may alias an input. */
+size_t epnet_rcnn_sample_rois_workspace_bytes(int b, int m, int g, int r);
+int epnet_rcnn_sample_rois(int b, int m, int g, int gc, int r, int fg_per_image, float fg_thresh, float cls_bg_thresh,
+                           float cls_bg_thresh_lo, double hard_bg_ratio, int aug_times, const float *rois,
+                           const float *gt_boxes3d, const float *fg_key, const float *slot_u,
+                           const unsigned char *keep_draw, const float *noise, void *workspace, size_t workspace_bytes,
+                           float *batch_rois, float *batch_gt_of_rois, float *batch_roi_iou, int *scene_info, int *src_inds,
+                           float *iou_src, int *tries, float *max_overlaps, int *gt_assignment, epnet_stream_t stream);
+
 /* ProposalLayer.forward after the box decoding, lib/rpn/proposal_layer.py:34-55 with distance_based_proposal :58-119
  * (distance_based != 0: two bins 0 < z <= 40 and 40 < z <= 80 with 70 % / 30 % of the pre- and post-NMS budgets, the far bin
  * falling back to the near bin's next boxes when it is empty) or score_based_proposal :121-142 (one bin), for all b
@@ -433,6 +475,37 @@ int epnet_roipool3d(int batch_size, int pts_num, int boxes_num, int feature_in_l
 int epnet_roipool3d_canonical(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num,
                               float pool_extra_width, const float *xyz, const float *rois, const float *pts_feature,
                               float *pooled_features, int *pooled_empty_flag, epnet_stream_t stream);
+
+/* The tail of ProposalTargetLayer.forward (lib/rpn/proposal_target_layer.py:16-83) in ONE launch: roipool3d_gpu on the
+ * enlarged ROIs, data_augmentation (:292-349) per ROI, the canonical transformation (:51-62) and the labels (:64-73).
+ * xyz (B,N,3), pts_feature (B,N,C); rois (B,R,7), gt_of_rois (B,R,7) and roi_iou (B,R) as epnet_rcnn_sample_rois returns them;
+ * aug (B,R,3) = [angle, scale, flip (+1 / -1)] per ROI, or NULL (AUG_DATA False: no augmentation step at all).
+ * Membership and the choice of the S rows are exactly epnet_roipool3d_canonical's on the ROI as given. All arithmetic below
+ * is fp32 in source order without contraction; cos / sin / atan2 are correctly rounded via double; pi and 2 pi are the fp32
+ * constants; sign(0) = 0.
+ *   box rule, applied to the ROI and to its ground-truth row [x, y, z, h, w, l, ry] (with aug):
+ *     beta = atan2(z, x), alpha = ((-sign(beta) * pi) / 2 + beta) + ry, ca = cos(angle), sa = sin(angle),
+ *     x' = x * ca + z * (-sa), z' = x * sa + z * ca, beta' = atan2(z', x'), ry' = ((sign(beta') * pi) / 2 + alpha) - beta',
+ *     columns 0..5 times scale, x times flip, ry'' = [flip == 1] * ry' + [flip == -1] * (sign(ry') * pi - ry').
+ *   a sampled point p (with aug): x1 = p.x * ca + p.z * (-sa), z1 = p.x * sa + p.z * ca, q = ((x1 * scale) * flip, p.y * scale,
+ *     z1 * scale); without aug q = p. With the augmented ROI A: d = q - A.centre, c = cos(A.ry), s = sin(A.ry),
+ *     sampled_pts row = (d.x * c + d.z * (-s), d.y, d.x * s + d.z * c).
+ *   ground truth G (augmented): m = A.ry mod 2 pi (the sign of the divisor, torch's %), e = G.centre - A.centre,
+ *     gt_out = (e.x * cos m + e.z * (-sin m), e.y, e.x * sin m + e.z * cos m, G.h, G.w, G.l, G.ry - m).
+ *   labels: valid = the box holds a point; reg_valid_mask = roi_iou > reg_fg_thresh && valid; cls_label = roi_iou >
+ *     cls_fg_thresh, -1 where cls_bg_thresh < roi_iou < cls_fg_thresh, -1 where not valid.
+ *   mask_score = the sum of feature column 0 over the S rows (per-thread partial sums of rows t, t + 256, ..., folded by a
+ *     butterfly over each wave and then over the 4 waves in order: fixed) divided by S; 0 when C == 0.
+ * Results, each a contiguous tensor of its own: sampled_pts (B*R,S,3), pts_feature_out (B*R,S,C), rois_out (B*R,7) augmented,
+ * gt_out (B*R,7) canonical, cls_label (B*R) i32, reg_valid_mask (B*R) i32, mask_score (B*R), pooled_empty_flag (B,R) i32.
+ * An empty ROI: flag 1, all S rows hold the point formula with p = 0 (what the reference's zero rows become), features 0,
+ * class -1, mask score 0. Every element of every output is written. Limits as epnet_roipool3d, checked before the launch. */
+int epnet_roipool3d_train(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num,
+                          float pool_extra_width, float reg_fg_thresh, float cls_fg_thresh, float cls_bg_thresh,
+                          const float *xyz, const float *pts_feature, const float *rois, const float *gt_of_rois,
+                          const float *roi_iou, const float *aug, float *sampled_pts, float *pts_feature_out,
+                          float *rois_out, float *gt_out, int *cls_label, int *reg_valid_mask, float *mask_score,
+                          int *pooled_empty_flag, epnet_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------
  * training losses (lib/net/train_functions.py:92-284 over lib/utils/loss_utils.py:79-350)
