@@ -312,6 +312,50 @@ def rcnn_targets_rows(args, report, timeit_pair):
                % (ms_host, ms_draw, ms_sample, sample_bytes, ms_cat, ms_pool))
 
 
+def kitti_eval_rows(args):
+    """the AP evaluator (epnet_amd.kitti_eval) on a seeded synthetic set: median wall time of the whole get_official_eval_result
+    (class Car) and of its phases, and the same set -- cut down to --kitti-eval-host-frames -- through the numpy restatement of
+    the reference's loops (tests/kitti_eval_restate.py) on one host core. No reference figure exists: the reference evaluator
+    is numba.cuda and cannot run on this hardware."""
+    import statistics
+    import time
+
+    import torch
+    from epnet_amd import kitti_eval, synth
+    frames = args.kitti_eval_frames
+    gts, dts = synth.kitti_eval_annos(frames, seed=3)
+    shape = {"frames": frames, "gt": int(sum(len(a["name"]) for a in gts)), "dt": int(sum(len(a["name"]) for a in dts)), "class": "Car"}
+    kitti_eval.get_official_eval_result(gts, dts, 0)   # warm-up
+    whole = []
+    for _ in range(args.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        result, ret = kitti_eval.get_official_eval_result(gts, dts, 0)
+        whole.append((time.perf_counter() - t0) * 1e3)
+    print(json.dumps({"op": "kitti_eval", "shape": shape, "ms": round(statistics.median(whole), 3), "reps": args.reps,
+                      "note": "get_official_eval_result, wall time; Car 3d AP (moderate) %.4f" % ret["Car_3d_moderate"]}), flush=True)
+    phases = {}
+    for _ in range(args.reps):
+        seconds = {}
+        kitti_eval.get_official_eval_result(gts, dts, 0, _profile=seconds)
+        for key, sec in seconds.items():
+            phases.setdefault(key, []).append(sec * 1e3)
+    for key in sorted(phases):
+        print(json.dumps({"op": "kitti_eval/" + key, "shape": shape, "ms": round(statistics.median(phases[key]), 3), "reps": args.reps,
+                          "note": "phase of get_official_eval_result, a device synchronisation either side"}), flush=True)
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tests"))
+    import kitti_eval_restate
+    n = min(frames, args.kitti_eval_host_frames)
+    t0 = time.perf_counter()
+    host_result, _ = kitti_eval_restate.get_official_eval_result(gts[:n], dts[:n], [0])
+    host_ms = (time.perf_counter() - t0) * 1e3
+    same = host_result == kitti_eval.get_official_eval_result(gts[:n], dts[:n], 0)[0]
+    print(json.dumps({"op": "kitti_eval/numpy_restatement", "shape": {"frames": n, "gt": int(sum(len(a["name"]) for a in gts[:n])), "dt": int(sum(len(a["name"]) for a in dts[:n])),
+                                "class": "Car"}, "ms": round(host_ms, 1), "reps": 1,
+                      "note": "one host core, %d of %d frames; same result string as the GPU on these frames: %s" % (n, frames, same)}),
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -320,7 +364,13 @@ def main():
     ap.add_argument("--rcnn-targets-only", action="store_true",
                     help="only the RCNN training targets (the sync-free RCNNTargetLayer against the existing ProposalTargetLayer)")
     ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
+    ap.add_argument("--kitti-eval-only", action="store_true",
+                    help="only the AP evaluator: get_official_eval_result and its phases on a synthetic set at KITTI-val scale")
+    ap.add_argument("--kitti-eval-frames", type=int, default=3769, help="frames of the synthetic set (KITTI val: 3769)")
+    ap.add_argument("--kitti-eval-host-frames", type=int, default=200, help="frames given to the numpy restatement on one host core")
     args = ap.parse_args()
+    if args.kitti_eval_only:
+        return kitti_eval_rows(args)
     import torch
     from epnet_amd import iou3d_cuda, iou3d_utils, kitti_utils, pointnet2_cuda as p2, roipool3d_cuda, synth
 

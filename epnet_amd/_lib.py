@@ -101,6 +101,12 @@ SIGNATURES = {
     "epnet_box_loss": (_i, [ctypes.c_longlong, _i, _d, _d, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "epnet_rpn_targets": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_kitti_overlaps": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_kitti_match": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_kitti_pr_workspace_bytes": (_sz, [_i, _i, _i]),
+    "epnet_kitti_pr": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "epnet_kitti_thresholds_host": (_i, [_vp, _i64, _i64, _i, _vp, _i, ctypes.POINTER(_i)]),
     "epnet_pts_in_boxes3d_host": (_i, [_vp, _vp, _vp, _i64, _i64]),
     "epnet_roipool3d_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64]),
 }

@@ -11,6 +11,8 @@ The reference's Python surface does bare top-level imports of its three extensio
 unmodified reference checkout runs on MI355X (its own Python surface on top of our C ABI).
 ``install_surface()`` additionally serves this package's surface modules under the reference's
 package paths for callers that do not have the reference tree on ``sys.path`` at all.
+``install_evaluator()`` serves the AP evaluator under ``tools.kitti_object_eval_python`` (tools/eval_rcnn.py:11), whose
+reference modules need numba and a CUDA device.
 """
 import importlib
 import sys
@@ -87,3 +89,20 @@ def install_callers(sync_free=False):
         sys.modules[dotted] = mod
         parent, leaf = dotted.rsplit(".", 1)
         setattr(sys.modules[parent], leaf, mod)
+
+
+_EVALUATOR = "tools.kitti_object_eval_python"
+
+
+def install_evaluator():
+    """serve ``epnet_amd.kitti_eval`` as ``tools.kitti_object_eval_python.evaluate`` / ``.eval`` / ``.kitti_common`` and its
+    ``rotate_iou_gpu_eval(boxes, query_boxes, criterion)`` as ``.rotate_iou``, so that ``from
+    tools.kitti_object_eval_python.evaluate import evaluate`` (tools/eval_rcnn.py:11) resolves without numba"""
+    mod = importlib.import_module("epnet_amd.kitti_eval")
+    rot = types.ModuleType(_EVALUATOR + ".rotate_iou")
+    rot.rotate_iou_gpu_eval = mod.rotate_iou_gpu_eval
+    for leaf, served in (("evaluate", mod), ("eval", mod), ("kitti_common", mod), ("rotate_iou", rot)):
+        dotted = _EVALUATOR + "." + leaf
+        _ensure_package(dotted)
+        sys.modules[dotted] = served
+        setattr(sys.modules[_EVALUATOR], leaf, served)

@@ -6,8 +6,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <string>
+#include <vector>
 
 #include "common.h"
 
@@ -166,5 +168,32 @@ extern "C" int epnet_roipool3d_host(const float *pts, const float *boxes3d, cons
                 if (C) memcpy(of + j * C, of + (j % cnt) * C, (size_t)C * sizeof(float));
             }
     }
+    return EPNET_OK;
+}
+
+// get_thresholds, eval.py:8-25
+extern "C" int epnet_kitti_thresholds_host(const double *matched, int64_t n, int64_t num_gt, int num_sample_pts, double *thresholds,
+                                           int capacity, int *count) {
+    EPNET_REQUIRE(n >= 0 && num_gt >= 0 && num_sample_pts >= 2 && capacity >= 0 && count);
+    EPNET_REQUIRE(n == 0 || matched);
+    std::vector<double> scores;
+    for (int64_t i = 0; i < n; ++i)
+        if (matched[i] == matched[i]) scores.push_back(matched[i]);
+    *count = 0;
+    if (scores.empty()) return EPNET_OK;
+    EPNET_REQUIRE(num_gt > 0 && (capacity == 0 || thresholds));
+    std::sort(scores.begin(), scores.end(), [](double a, double b) { return a > b; });
+    const int64_t m = (int64_t)scores.size();
+    double current_recall = 0;
+    int k = 0;
+    for (int64_t i = 0; i < m; ++i) {
+        const double l_recall = (double)(i + 1) / (double)num_gt;
+        const double r_recall = i < m - 1 ? (double)(i + 2) / (double)num_gt : l_recall;
+        if ((r_recall - current_recall) < (current_recall - l_recall) && i < m - 1) continue;
+        if (k >= capacity) return EPNET_ENOMEM;
+        thresholds[k++] = scores[i];
+        current_recall += 1 / (num_sample_pts - 1.0);
+    }
+    *count = k;
     return EPNET_OK;
 }

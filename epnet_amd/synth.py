@@ -110,3 +110,55 @@ def proposal_boxes(num, seed=0, num_objects=40, jitter=1.0):
     pick[:, 6] += (torch.rand((num,), generator=g) * 2 - 1) * 0.3
     scores = torch.rand((num,), generator=g, dtype=torch.float32)
     return pick.contiguous(), scores
+
+
+def kitti_eval_annos(frames, seed=0, mean_gt=6.0, mean_dt=10.0):
+    """(gt_annos, dt_annos) for the AP evaluator (epnet_amd.kitti_eval), as get_label_annos returns them: numpy dicts, not
+    tensors -- the evaluator's input is label files. Per frame about mean_gt ground truths (Car / Van / Pedestrian / Cyclist /
+    DontCare, all occlusion levels, truncations and 2D heights either side of the difficulty limits) and about mean_dt
+    detections: jittered copies of ground truths, duplicates, boxes over DontCare regions and pure false positives.
+    KITTI val is 3769 frames."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    names = ["Car", "Car", "Car", "Van", "Pedestrian", "Cyclist", "DontCare"]
+    dims_of = {"Car": (3.9, 1.5, 1.6), "Van": (5.0, 2.2, 1.9), "Pedestrian": (0.8, 1.8, 0.6), "Cyclist": (1.8, 1.7, 0.6)}
+    keys = ("name", "truncated", "occluded", "alpha", "bbox", "dimensions", "location", "rotation_y", "score")
+
+    def pack(rows):
+        out = {"name": np.array([r[0] for r in rows], dtype="<U16")}
+        for i, (key, width) in enumerate((("truncated", 1), ("occluded", 1), ("alpha", 1), ("bbox", 4), ("dimensions", 3),
+                                          ("location", 3), ("rotation_y", 1), ("score", 1)), start=1):
+            a = np.array([r[i] for r in rows], np.int64 if key == "occluded" else np.float64)
+            out[key] = a.reshape(-1, width) if width > 1 else a.reshape(-1)
+        return out
+
+    gts, dts = [], []
+    for _ in range(frames):
+        g, d = [], []
+        for _ in range(int(rng.poisson(mean_gt))):
+            name = names[int(rng.integers(len(names)))]
+            left, top, height = rng.uniform(0, 1100), rng.uniform(120, 250), float(rng.choice([20.0, 30.0, 45.0, 70.0, 120.0]))
+            box = [left, top, left + height * rng.uniform(0.6, 2.0), top + height]
+            if name == "DontCare":
+                g.append((name, -1.0, -1, -10.0, box, [-1.0] * 3, [-1000.0] * 3, -10.0, 0.0))
+                continue
+            l, h, w = (v * rng.uniform(0.85, 1.15) for v in dims_of[name])
+            g.append((name, float(rng.choice([0.0, 0.1, 0.2, 0.4, 0.6])), int(rng.integers(0, 4)), rng.uniform(-math.pi, math.pi), box,
+                      [l, h, w], [rng.uniform(-30, 30), rng.uniform(1.3, 1.9), rng.uniform(4, 70)], rng.uniform(-math.pi, math.pi), 0.0))
+        share = mean_dt / max(mean_gt, 1.0)
+        for row in g:
+            for _ in range(int(rng.poisson(share * 0.8))):
+                s = 0.03 if rng.uniform() < 0.7 else 0.15
+                cls = "Car" if row[0] == "DontCare" else row[0]
+                box = [v + rng.normal(0, s * 30) for v in row[4]]
+                dims = [abs(v) * (1 + rng.normal(0, s)) for v in (row[5] if row[0] != "DontCare" else dims_of["Car"])]
+                loc = [v + rng.normal(0, s * 3) for v in (row[6] if row[0] != "DontCare" else (0.0, 1.6, 75.0))]
+                d.append((cls, 0.0, 0, row[3] + rng.normal(0, 0.2), box, dims, loc, row[7] + rng.normal(0, s), rng.uniform(0.05, 1.0)))
+        for _ in range(int(rng.poisson(share * 0.2 * mean_gt))):
+            left, top, height = rng.uniform(0, 1100), rng.uniform(120, 250), float(rng.choice([20.0, 30.0, 45.0]))
+            d.append(("Car", 0.0, 0, rng.uniform(-3, 3), [left, top, left + height * 1.5, top + height], list(dims_of["Car"]),
+                      [rng.uniform(-30, 30), 1.6, rng.uniform(4, 70)], rng.uniform(-3, 3), rng.uniform(0.05, 0.5)))
+        gts.append(pack(g))
+        dts.append(pack(d))
+    assert keys == tuple(gts[0])
+    return gts, dts

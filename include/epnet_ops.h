@@ -579,6 +579,62 @@ int epnet_rpn_targets(int b, int n, int g, float extra_width, const float *pts, 
                       const float *gt_alpha, const float *aug, float *pts_out, float *gt_out, int *cls_label,
                       float *reg_label, epnet_stream_t stream);
 
+/* ---- The KITTI AP evaluator (tools/kitti_object_eval_python: rotate_iou.py:18-296, a numba.cuda kernel, and eval.py:84-332,
+ * numba CPU JIT). All frames of a call are ragged: frame f owns rows *_off[f] .. *_off[f+1] of the arrays that go with the
+ * offset array (F+1 int32 each) and the dt_num[f] x gt_num[f] float64 block at ov_off[f] (F+1 int64), detection-major as
+ * eval.py:204 indexes it (overlaps[j, i], j = detection, i = ground truth). Nothing is padded; no kernel reads at or past
+ * *_off[F]. The offsets live on the device, so the caller states the largest per-frame counts (max_*); beyond the limits
+ * below the calls return EPNET_ELIMIT before any launch. These are end-of-epoch calls: asynchronous on `stream` like every
+ * other entry point, but combo_* arrays are HOST memory (at most EPNET_KITTI_MAX_COMBOS entries, copied at the call). */
+#define EPNET_KITTI_MAX_DT 1024        /* detections per frame */
+#define EPNET_KITTI_MAX_GT 256         /* ground-truth rows per frame */
+#define EPNET_KITTI_MAX_DC 256         /* DontCare boxes per frame */
+#define EPNET_KITTI_MAX_COMBOS 16      /* (difficulty, min_overlap) combinations per call */
+#define EPNET_KITTI_MAX_THRESHOLDS 64  /* score thresholds per combination (the evaluator uses up to 41) */
+
+/* The per-frame blocks of calculate_iou_partly (eval.py:334-408) for one metric, rows = the frame's `boxes` (detections, as
+ * eval.py:467 passes them), cols = its `query_boxes`; out[ov_off[f] + j * cols_f + i], float64.
+ *   metric 0, boxes (n,4) f64: image_box_overlap (eval.py:85-111) in float64, source order; criterion -1 (IoU), 0 (over the row
+ *     box's area, the DontCare pass of eval.py:247) or 1;
+ *   metric 1, boxes (n,5) f64 [x, z, l, w, ry]: rotate_iou_gpu_eval(criterion -1): cast to float32, devRotateIoUEval(col, row)
+ *     (rotate_iou.py:293: the query box is rbox1) in float32, source order, cos / sin correctly rounded via double; widened;
+ *   metric 2, boxes (n,7) f64 [x, y, z, l, h, w, ry]: d3_box_overlap (eval.py:120-152): the float32 intersection area of columns
+ *     [0,2,3,5,6], then height overlap min(y) - max(y - h), volumes and the ratio in float64, stored through float32 as the
+ *     reference's `rinc` array does; criterion -1.
+ * Frames with no rows or no cols write nothing. max_rows <= EPNET_KITTI_MAX_DT, max_cols <= EPNET_KITTI_MAX_GT. */
+int epnet_kitti_overlaps(int metric, int criterion, int frames, int max_rows, int max_cols, const int *row_off,
+                         const int *col_off, const int64_t *ov_off, const double *row_boxes, const double *col_boxes,
+                         double *overlaps, epnet_stream_t stream);
+
+/* Pass 1, compute_statistics_jit(thresh = 0, compute_fp = False) (eval.py:486-498), of every frame for every combination
+ * c = (combo_difficulty[c], combo_min_overlap[c]) in one launch. ignored_gt (num_difficulty, total_gt) and ignored_dt
+ * (num_difficulty, total_dt) are clean_data's tables (1 / 0 / -1) as int32; dt_score (total_dt) f64. matched (combos, total_gt)
+ * f64: the matched detection's score where the reference appends one to `thresholds`, NaN elsewhere; every element is
+ * written. min_overlap >= 0 (else EPNET_EINVAL). The result is that of the sequential loops: among equal scores the lowest
+ * detection index wins. */
+int epnet_kitti_match(int frames, int total_gt, int total_dt, int max_gt, int max_dt, int num_difficulty, int combos,
+                      const int *combo_difficulty, const double *combo_min_overlap, const int *gt_off, const int *dt_off,
+                      const int64_t *ov_off, const double *overlaps, const double *dt_score, const int *ignored_gt,
+                      const int *ignored_dt, double *matched, epnet_stream_t stream);
+
+/* bytes of epnet_kitti_pr's workspace (the per-frame partial sums); pure arithmetic; 0 for an empty problem or outside the limits */
+size_t epnet_kitti_pr_workspace_bytes(int frames, int combos, int tstride);
+
+/* Pass 2, fused_compute_statistics (eval.py:285-331): compute_statistics_jit(compute_fp = True) of every frame for every
+ * combination c and each of its combo_num_thresholds[c] <= tstride thresholds (thresholds (combos, tstride) f64, device), in
+ * one launch; the per-frame tp / fp / fn and similarity go to the workspace and a second kernel adds them in an order that
+ * depends on `frames` alone (no atomics: same inputs, same bits). pr_counts (combos, tstride, 3) i32 = tp, fp, fn and
+ * pr_similarity (combos, tstride) f64 (the sum of (1 + cos(gt_alpha - dt_alpha)) / 2 over the true positives, when compute_aos);
+ * rows t >= combo_num_thresholds[c] are written as zeros. metric 0 runs the DontCare pass of eval.py:246-259 on dt_bbox
+ * (total_dt,4) and dc_bbox (rows of dc_off, 4), both f64. A detection is dropped by a threshold when score < threshold. */
+int epnet_kitti_pr(int frames, int total_gt, int total_dt, int max_gt, int max_dt, int max_dc, int num_difficulty, int combos,
+                   int tstride, int metric, int compute_aos, const int *combo_difficulty, const double *combo_min_overlap,
+                   const int *combo_num_thresholds, const int *gt_off, const int *dt_off, const int *dc_off,
+                   const int64_t *ov_off, const double *overlaps, const double *dt_score, const int *ignored_gt,
+                   const int *ignored_dt, const double *dt_bbox, const double *dc_bbox, const double *gt_alpha,
+                   const double *dt_alpha, const double *thresholds, void *workspace, size_t workspace_bytes,
+                   int *pr_counts, double *pr_similarity, epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
@@ -590,6 +646,12 @@ int epnet_roipool3d_host(const float *pts, const float *boxes3d, const float *pt
                          float *pooled_pts, float *pooled_features, int64_t *pooled_empty_flag,
                          int64_t boxes_num, int64_t pts_num, int64_t feature_len,
                          int64_t sampled_pts_num);
+
+/* get_thresholds (eval.py:8-25), a host op: `matched` (n) f64 HOST memory as epnet_kitti_match wrote it (NaN entries are
+ * skipped), sorted descending, then the recall rule for num_sample_pts points in float64. Writes at most `capacity`
+ * thresholds and their number to *count; EPNET_ENOMEM if there are more. */
+int epnet_kitti_thresholds_host(const double *matched, int64_t n, int64_t num_gt, int num_sample_pts,
+                                double *thresholds, int capacity, int *count);
 
 #ifdef __cplusplus
 }
