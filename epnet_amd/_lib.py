@@ -89,6 +89,9 @@ SIGNATURES = {
     "epnet_rpn_proposals": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "epnet_rcnn_detections_workspace_bytes": (_sz, [_i, _i]),
     "epnet_rcnn_detections": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "epnet_eval_recall_workspace_bytes": (_sz, [_i, _i, _i]),
+    "epnet_eval_recall": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_kitti_records": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_nms_workspace_bytes": (_sz, [_i]),
     "epnet_nms": (_i, [_vp, _i, _f, _vp, _sz, _vp, _vp, _vp]),
     "epnet_nms_normal": (_i, [_vp, _i, _f, _vp, _sz, _vp, _vp, _vp]),

@@ -6,6 +6,8 @@ count (iou3d.cpp:73-120) -- but mask AND greedy sweep run on the device; only th
 (N*8 B instead of the reference's N*ceil(N/64)*8 B mask) cross PCIe. ``nms_device`` /
 ``nms_normal_device`` expose the all-device form for callers that do not need a host list.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -183,6 +185,80 @@ def rcnn_detections_gpu(boxes3d, raw_scores, norm_scores, score_thresh, nms_thre
     with on_device_of(raw_scores) as s:
         _lib.check(l.epnet_rcnn_detections(b, m, pb, pr, pn, float(score_thresh), float(nms_thresh), ws.data_ptr(), ws.numel(),
                                            ob, os_, oc, s), "rcnn_detections")
+    return 1
+
+
+def _opt(t, name, dtype, count):
+    """device address of an optional tensor (None -> NULL)"""
+    if t is None:
+        return None
+    p = dev_ptr(t, name, dtype)
+    need(t, count, name)
+    return p
+
+
+@writes("scene_stats", "seg_counts", "totals", "gt_max_pred", "gt_max_roi", "pred_max_iou")
+def eval_recall_gpu(pred_boxes3d, roi_boxes3d, gt_boxes3d, thresholds, seg_result, rpn_cls_label, scene_stats, seg_counts=None,
+                    totals=None, gt_max_pred=None, gt_max_roi=None, pred_max_iou=None):
+    """tools/eval_rcnn.py:598-632 for the whole batch, no host sync: pred_boxes3d (B,M,7), roi_boxes3d (B,M,7) or None,
+    gt_boxes3d (B,G,7..16) zero-padded, thresholds a sequence of at most 8 Python floats, seg_result / rpn_cls_label (B,N) int32
+    or both None -> scene_stats (B, 1 + 2 T) int32 = [num_gt, recalled_refined[T], recalled_roi[T]], seg_counts (3) int64 =
+    [correct, fg, pos] (None exactly when the segmentation inputs are) and, where given, totals (1 + 2 T) int64 (added to),
+    gt_max_pred / gt_max_roi (B,G), pred_max_iou (B,M) (not in the reference extension; see epnet_ops.h)"""
+    if pred_boxes3d.dim() != 3 or pred_boxes3d.shape[2] != 7:
+        raise RuntimeError("pred_boxes3d must be (B, M, 7)")
+    if gt_boxes3d.dim() != 3 or gt_boxes3d.shape[0] != pred_boxes3d.shape[0]:
+        raise RuntimeError("gt_boxes3d must be (B, G, 7..16)")
+    if (seg_result is None) != (rpn_cls_label is None) or (seg_result is None) != (seg_counts is None):
+        raise RuntimeError("seg_result, rpn_cls_label and seg_counts are given together or not at all")
+    b, m, g, gc = pred_boxes3d.shape[0], pred_boxes3d.shape[1], gt_boxes3d.shape[1], gt_boxes3d.shape[2]
+    thr = [float(t) for t in thresholds]
+    nt = len(thr)
+    I, L = torch.int32, torch.int64
+    pp = dev_ptr(pred_boxes3d, "pred_boxes3d", _F)
+    pr = _opt(roi_boxes3d, "roi_boxes3d", _F, b * m * 7)
+    pg = dev_ptr(gt_boxes3d, "gt_boxes3d", _F)
+    n = 0
+    ps = pl = None
+    if seg_result is not None:
+        if seg_result.dim() != 2 or seg_result.shape[0] != b or seg_result.shape != rpn_cls_label.shape:
+            raise RuntimeError("seg_result and rpn_cls_label must both be (B, N)")
+        n = seg_result.shape[1]
+        ps, pl = dev_ptr(seg_result, "seg_result", I), dev_ptr(rpn_cls_label, "rpn_cls_label", I)
+    po = dev_ptr(scene_stats, "scene_stats", I)
+    need(scene_stats, b * (1 + 2 * nt), "scene_stats")
+    outs = [_opt(seg_counts, "seg_counts", L, 3), _opt(totals, "totals", L, 1 + 2 * nt), _opt(gt_max_pred, "gt_max_pred", _F, b * g),
+            _opt(gt_max_roi, "gt_max_roi", _F, b * g), _opt(pred_max_iou, "pred_max_iou", _F, b * m)]
+    l = _lib.lib()
+    ws_bytes = l.epnet_eval_recall_workspace_bytes(b, m, g)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=pred_boxes3d.device)
+    host_thr = (ctypes.c_float * max(nt, 1))(*thr)
+    with on_device_of(pred_boxes3d) as s:
+        _lib.check(l.epnet_eval_recall(b, m, g, gc, n, nt, ctypes.cast(host_thr, ctypes.c_void_p), pp, pr, pg, ps, pl, ws.data_ptr(),
+                                       ws.numel(), po, *outs, s), "eval_recall")
+    return 1
+
+
+@writes("records", "rec_count", "bbox_raw", "valid")
+def kitti_records_gpu(boxes3d, scores, count, P2, img_shape, records, rec_count, bbox_raw=None, valid=None):
+    """save_kitti_format (tools/eval_rcnn.py:76-101) for the whole batch in one launch: boxes3d (B,M,7), scores (B,M), count (B)
+    int32 or None (all M rows), P2 (B,3,4), img_shape (B,2) int32 [h, w] -> records (B,M,13) float64 (the valid rows, compacted,
+    zero rows behind), rec_count (B) int32 and, where given, bbox_raw (B,M,4), valid (B,M) int32 (not in the reference
+    extension; see epnet_ops.h)"""
+    if boxes3d.dim() != 3 or boxes3d.shape[2] != 7:
+        raise RuntimeError("boxes3d must be (B, M, 7)")
+    b, m = boxes3d.shape[0], boxes3d.shape[1]
+    I = torch.int32
+    pb, ps = dev_ptr(boxes3d, "boxes3d", _F), dev_ptr(scores, "scores", _F)
+    need(scores, b * m, "scores")
+    pc = _opt(count, "count", I, b)
+    pp, pi = dev_ptr(P2, "P2", _F), dev_ptr(img_shape, "img_shape", I)
+    need(P2, b * 12, "P2"); need(img_shape, b * 2, "img_shape")
+    pr, pn = dev_ptr(records, "records", torch.float64), dev_ptr(rec_count, "rec_count", I)
+    need(records, b * m * 13, "records"); need(rec_count, b, "rec_count")
+    px, pv = _opt(bbox_raw, "bbox_raw", _F, b * m * 4), _opt(valid, "valid", I, b * m)
+    with on_device_of(boxes3d) as s:
+        _lib.check(_lib.lib().epnet_kitti_records(b, m, pb, ps, pc, pp, pi, pr, pn, px, pv, s), "kitti_records")
     return 1
 
 

@@ -432,6 +432,65 @@ int epnet_rcnn_detections(int b, int m, const float *boxes3d, const float *raw_s
                           float score_thresh, float nms_thresh, void *workspace, size_t workspace_bytes,
                           float *det_boxes3d, float *det_scores, int *det_count, epnet_stream_t stream);
 
+/* The recall and segmentation counts of eval_one_epoch_joint, tools/eval_rcnn.py:598-632, for all b scenes in one call with no
+ * host synchronisation, no allocation and no float atomics (the reference trims the ground truth on the host, calls
+ * boxes_iou3d_gpu twice per scene and reads eleven scalars back). pred_boxes3d (b,m,7) the refined boxes; roi_boxes3d (b,m,7)
+ * the ROIs, or NULL (the ROI counters are then written as 0); gt_boxes3d (b,g,gc), 7 <= gc <= 16, zero-padded as collate_batch
+ * pads (may be NULL when g == 0); thresholds: nt <= 8 floats in HOST memory, copied at the call (they travel by value in the
+ * kernel arguments: the call is graph-capturable); seg_result / rpn_cls_label (b,n) i32, both NULL together with seg_counts
+ * (RPN.FIXED). Per scene:
+ *   padding (:600-607): num_gt = 1 + the last row whose fp32 sum over all gc columns, taken in ascending column order, is not
+ *     0; zero rows in front of it stay (boxes with IoU 0). A scene WITHOUT such a row contributes nothing (:606, tmp_idx < 0):
+ *     num_gt 0, all its counters 0.
+ *   iou[i,j] for i < m, j < num_gt: the 3-D IoU of (box_i, gt_j), bit for bit epnet_boxes_iou3d's value, for both box sets.
+ *   gt_max[j] = max over i of iou[i,j] (:611, :622); a NaN IoU wins over every number, as torch.max propagates it.
+ *   recalled[t] = the number of j < num_gt with gt_max[j] > thresholds[t]: strict, in fp32, against the float the caller passed
+ *     (a NaN maximum is recalled at no threshold), for the refined set and for the ROI set (:614-615, :624-625).
+ * Over the WHOLE batch tensor, as :628-630 does inside its per-scene loop: correct = the elements with label > 0 and seg ==
+ * label, fg = those with label > 0, pos = those with seg > 0.
+ * Results, every element of every given output written: scene_stats (b, 1 + 2 nt) i32 = [num_gt, recalled_refined[nt],
+ * recalled_roi[nt]]; seg_counts (3) i64 = [correct, fg, pos], NULL exactly when the segmentation inputs are; optional (NULL
+ * allowed): totals (1 + 2 nt) i64, the caller's running epoch sums, to which the column sums of scene_stats are ADDED (integer
+ * adds: their order does not matter); gt_max_pred / gt_max_roi (b,g), 0 in the columns at or beyond num_gt (gt_max_roi: all 0
+ * without roi_boxes3d); pred_max_iou (b,m) = max over j < num_gt of iou[i,j] for the refined boxes (refined_iou of :612, NaN
+ * wins), 0 where the scene has no ground truth. Limits, checked before any launch: 1 <= m <= 4096, g >= 0, b <= 65535, nt <= 8,
+ * else EPNET_ELIMIT; a NULL required pointer, gc out of range, or seg_counts given without its inputs (or the reverse):
+ * EPNET_EINVAL; a workspace below epnet_eval_recall_workspace_bytes(b, m, g) (pure arithmetic: the per-workgroup segmentation
+ * sums, the (b,2,g) column maxima and the (b,g,m) IoU matrix of the refined boxes, each rounded up to 16 bytes; 0 outside the
+ * limits): EPNET_ENOMEM; b == 0 returns EPNET_OK and writes nothing. PRECONDITION: no output may alias an input. */
+size_t epnet_eval_recall_workspace_bytes(int b, int m, int g);
+int epnet_eval_recall(int b, int m, int g, int gc, int n, int nt, const float *thresholds, const float *pred_boxes3d,
+                      const float *roi_boxes3d, const float *gt_boxes3d, const int *seg_result, const int *rpn_cls_label,
+                      void *workspace, size_t workspace_bytes, int *scene_stats, int64_t *seg_counts, int64_t *totals,
+                      float *gt_max_pred, float *gt_max_roi, float *pred_max_iou, epnet_stream_t stream);
+
+/* save_kitti_format, tools/eval_rcnn.py:76-101, for all b scenes in ONE launch: the KITTI result records of the boxes instead of
+ * a text file per scene. boxes3d (b,m,7) [x,y,z,h,w,l,ry], scores (b,m); count (b) i32 on the device or NULL: with a count only
+ * the first min(max(count[k], 0), m) rows of scene k are boxes (epnet_rcnn_detections' det_count), with NULL all m rows are
+ * (--save_result on ROIs and refined boxes); P2 (b,3,4) f32 the camera matrix of each scene, img_shape (b,2) i32 = [h, w].
+ * All arithmetic is fp32 in source order without contraction; cos / sin / atan2 are correctly rounded via double, divisions
+ * correctly rounded, pi is the fp32 constant, sign(0) = 0 (the conventions of epnet_roipool3d_train). Per box:
+ *   corners (kitti_utils.py:66-103), k = 0..7: xc = (l/2, l/2, -l/2, -l/2, l/2, l/2, -l/2, -l/2), yc = (0, 0, 0, 0, -h, -h, -h, -h),
+ *     zc = (w/2, -w/2, -w/2, w/2, w/2, -w/2, -w/2, w/2), c = cos(ry), s = sin(ry),
+ *     X = x + (xc * c + zc * s), Y = y + yc, Z = z + (xc * (-s) + zc * c).
+ *   projection (calibration.py:106-118): p_r = ((X * P[r][0] + Y * P[r][1]) + Z * P[r][2]) + P[r][3], u = p_0 / p_2, v = p_1 / p_2.
+ *   image box: (min u, min v, max u, max v) over the eight corners, a NaN propagating as np.min does; then x1, x2 clipped to
+ *     [0, w - 1] and y1, y2 to [0, h - 1] (a NaN stays).
+ *   validity (:85-87): (x2 - x1) < (float)(w * 0.8) && (y2 - y1) < (float)(h * 0.8), the products in double as Python's and
+ *     rounded to fp32; a row with a NaN image coordinate is not valid.
+ *   alpha (:94-96): beta = atan2(z, x), alpha = ((-sign(beta) * pi) / 2 + beta) + ry (epnet_roipool3d_train's formula, in fp32:
+ *     DESIGN.md "Evaluation epoch").
+ *   text round trip: each value of [alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score] becomes r4(v) = rint((double)v * 1e4) /
+ *     1e4 in double (csrc/r4.h): exactly the double that printing v with %.4f and parsing the text back gives; non-finite values
+ *     pass through.
+ * Results: records (b,m,13) f64 = the valid rows of each scene, compacted in input order, zero rows behind; rec_count (b) i32;
+ * optional (NULL allowed) bbox_raw (b,m,4) f32 = the clipped, unrounded image boxes of ALL rows and valid (b,m) i32, both zero in
+ * the rows at or beyond the count. Every element of every given output is written. 1 <= m <= 4096 and b <= 65535, else
+ * EPNET_ELIMIT before the launch; b == 0 returns EPNET_OK. PRECONDITION: no output may alias an input. */
+int epnet_kitti_records(int b, int m, const float *boxes3d, const float *scores, const int *count, const float *P2,
+                        const int *img_shape, double *records, int *rec_count, float *bbox_raw, int *valid,
+                        epnet_stream_t stream);
+
 /* bytes of device scratch epnet_nms / epnet_nms_normal need for `boxes_num` boxes */
 size_t epnet_nms_workspace_bytes(int boxes_num);
 
