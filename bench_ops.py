@@ -4,7 +4,7 @@ iou3d (rotated overlap / IoU, both NMS flavours), roipool3d, three_nn / three_in
 gradient ops, at the shapes of the reference's rcnn_online step. One JSON line per op:
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
-    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only]
+    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only]
 """
 import argparse
 import json
@@ -222,6 +222,138 @@ def loss_rows(args, report, timeit_pair):
                    % (ms_ref, ms_free, ms_fused2, close))
 
 
+# ---- the optimiser step composed from stock torch calls (the comparator of epnet_amd.optim.FusedAdamOneCycle) -------------------------
+class ComposedAdamOneCycle:
+    """the reference's adam_onecycle step (tools/train_utils/train_utils.py:126-136) from stock torch calls: clip_grad_norm_, a
+    host-side one-cycle schedule that sets lr and beta1 as Python floats, the true-weight-decay loop (one mul_ per trainable
+    parameter) and torch.optim.Adam.step(); zero_grad() is stock (gradients become None)"""
+
+    def __init__(self, params, total_steps, lr_max=0.002, moms=(0.95, 0.85), div_factor=10.0, pct_start=0.4, wd=0.001, beta2=0.99,
+                 eps=1e-8, grad_norm_clip=1.0):
+        import torch
+        self.params = [p for p in params if p.requires_grad]
+        self.total_steps, self.lr_max, self.moms, self.low = total_steps, lr_max, tuple(moms), lr_max / div_factor
+        self.border, self.wd, self.beta2, self.clip, self.it = int(total_steps * pct_start), wd, beta2, grad_norm_clip, 0
+        self.adam = torch.optim.Adam(self.params, lr=self.low, betas=(self.moms[0], beta2), eps=eps, weight_decay=0)
+        self.last = None
+
+    def schedule(self, it):
+        import math
+        it = min(it, self.total_steps - 1)
+
+        def anneal(start, end, pct):
+            return end + (start - end) / 2 * (math.cos(math.pi * pct) + 1)
+        if it >= self.border:
+            pct = (it - self.border) / (self.total_steps - self.border)
+            return anneal(self.lr_max, self.low / 1e4, pct), anneal(self.moms[1], self.moms[0], pct)
+        pct = it / self.border
+        return anneal(self.low, self.lr_max, pct), anneal(self.moms[0], self.moms[1], pct)
+
+    def zero_grad(self):
+        self.adam.zero_grad()
+
+    def step(self):
+        import torch
+        norm = torch.nn.utils.clip_grad_norm_(self.params, self.clip)
+        lr, mom = self.schedule(self.it)
+        self.it += 1
+        for group in self.adam.param_groups:
+            group["lr"], group["betas"] = lr, (mom, self.beta2)
+        with torch.no_grad():
+            for p in self.params:
+                if p.requires_grad:
+                    p.mul_(1 - self.wd * lr)
+        self.adam.step()
+        self.last = (norm, lr, mom)
+
+
+def optim_rows(args, report):
+    """one optimiser step over the two-stream model's parameter list (bench_step.build_model(image=True): 15.7 M parameters) with
+    stored gradients: FusedAdamOneCycle (three launches) against ComposedAdamOneCycle, ALTERNATING inside one call; the gradients
+    are put back outside the timed region (the fused step zeroes them, the composed clip scales them)"""
+    import statistics
+    import torch
+    import bench_step
+    from epnet_amd import optim
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model_f = bench_step.build_model(image=True).to(dev)
+    model_c = bench_step.build_model(image=True).to(dev)
+    model_c.load_state_dict(model_f.state_dict())
+    steps = 2 * (3 + args.reps) + 1           # the pairs, then the bucket-view loop
+    fused = optim.FusedAdamOneCycle(model_f, steps)
+    params_f = fused.params
+    name_of = {id(p): n for n, p in model_f.named_parameters()}
+    by_name = dict(model_c.named_parameters())
+    params_c = [by_name[name_of[id(p)]] for p in params_f]
+    composed = ComposedAdamOneCycle(params_c, steps)
+    g = torch.Generator(device=dev).manual_seed(1)
+    master = [torch.randn(p.shape, generator=g, device=dev) * 1e-3 for p in params_f]
+    for p, q, m in zip(params_f, params_c, master):
+        p.grad, q.grad = m.clone(), m.clone()
+    grads_f, grads_c = [p.grad for p in params_f], [q.grad for q in params_c]
+    n = sum(p.numel() for p in params_f)
+
+    def bucket_views():
+        """move params_f's gradients into one flat bucket, each at element offset 1, 2 or 3 (mod 4)"""
+        at, slots = 0, []
+        for k, p in enumerate(params_f):
+            at = (at + 3) // 4 * 4 + 1 + k % 3
+            slots.append(at)
+            at += p.numel()
+        bucket = torch.zeros((at + 4,), device=dev)
+        for p, slot in zip(params_f, slots):
+            p.grad = bucket[slot:slot + p.numel()].view(p.shape)
+        return [p.grad for p in params_f]
+    if args.optim_side == "fused_views":
+        grads_f = bucket_views()
+
+    def refill():
+        torch._foreach_copy_(grads_f, master)
+        torch._foreach_copy_(grads_c, master)
+        torch.cuda.synchronize()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+    sides = {"both": (True, True), "fused": (True, False), "fused_views": (True, False), "composed": (False, True)}[args.optim_side]
+    tf, tc = [], []
+    for k in range(3 + args.reps):
+        refill()
+        a = timed(fused.step) if sides[0] else 0.0
+        b = timed(composed.step) if sides[1] else 0.0
+        if k == 0 and all(sides):   # one step from the same state: the two forms differ in rounding order only
+            diff = max(float((p.detach() - q.detach()).abs().max()) for p, q in zip(params_f, params_c))
+        if k >= 3:
+            tf.append(a); tc.append(b)
+    stats = fused.stats.tolist()
+    shape = {"tensors": len(params_f), "parameters": n, "reps": args.reps}
+    if not all(sides):       # one side alone, for a kernel trace: its own op name, and no bytes claimed for the composition
+        side_ms = statistics.median(tf) if sides[0] else statistics.median(tc)
+        return report("adam_onecycle_step/%s_alone" % args.optim_side, shape, side_ms, n * 36 if sides[0] else 0,
+                      "side %s only (for a kernel trace)" % args.optim_side)
+    report("adam_onecycle_step", shape, statistics.median(tf), n * 36,
+           "three launches, no host scalar; composed (clip_grad_norm_ + %d decay mul_ + stock Adam + host schedule): %.4f ms; fused lower in "
+           "%d of %d alternating pairs; max |p_fused - p_composed| after the first step %.2e; total_norm %.6f coef %.6f; algorithmic bytes: "
+           "4 (norm) + 16 read + 12 written + 4 (gradient zeroed) per parameter"
+           % (len(params_c), statistics.median(tc), sum(a < b for a, b in zip(tf, tc)), len(tf), diff, stats[0], stats[1]))
+    # the same step with every gradient a view at element offset 1, 2 or 3 (mod 4) of one flat bucket, as
+    # DistributedDataParallel(gradient_as_bucket_view=True) lays them out: g goes through dword accesses, p / m / v stay 16-byte
+    views = bucket_views()
+    tv = []
+    for k in range(3 + args.reps):           # the first step rebuilds the device tables; it is one of the three warm-up steps
+        torch._foreach_copy_(views, master)
+        torch.cuda.synchronize()
+        ms = timed(fused.step)
+        if k >= 3:
+            tv.append(ms)
+    report("adam_onecycle_step/bucket_views", shape, statistics.median(tv), n * 36,
+           "the same step with every gradient a view at element offset 1, 2 or 3 (mod 4) of one flat bucket: g in dword accesses, "
+           "p / m / v 16-byte; in a loop of its own after the pairs above (fused with gradient tensors of their own there: %.4f ms)"
+           % statistics.median(tf))
+
+
 def targets_rows(args, report, timeit_pair):
     """the fused RPN training targets (augmentation + labels, one launch: epnet_amd/rpn_target_layer.py) against the stock
     composition bench_step.rpn_labels (labels only, (B,N,G,3) temporaries), alternating inside one call, at 2 / 16 / 256 scenes x
@@ -364,6 +496,11 @@ def main():
     ap.add_argument("--rcnn-targets-only", action="store_true",
                     help="only the RCNN training targets (the sync-free RCNNTargetLayer against the existing ProposalTargetLayer)")
     ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
+    ap.add_argument("--optim-only", action="store_true",
+                    help="only the optimiser step: FusedAdamOneCycle against the stock-torch composition on the two-stream model's parameters")
+    ap.add_argument("--optim-side", default="both", choices=["both", "fused", "fused_views", "composed"],
+                    help="with --optim-only: run one side alone (what a kernel trace of launches per step needs); fused_views: the fused "
+                         "side with every gradient a view at an odd offset of one bucket")
     ap.add_argument("--kitti-eval-only", action="store_true",
                     help="only the AP evaluator: get_official_eval_result and its phases on a synthetic set at KITTI-val scale")
     ap.add_argument("--kitti-eval-frames", type=int, default=3769, help="frames of the synthetic set (KITTI val: 3769)")
@@ -482,6 +619,8 @@ def main():
         return stage2_infer()
     if args.loss_only:
         return loss_rows(args, report, timeit_pair)
+    if args.optim_only:
+        return optim_rows(args, report)
     if args.targets_only:
         return targets_rows(args, report, timeit_pair)
     if args.rcnn_targets_only:

@@ -8,7 +8,7 @@
     python bench_step.py --infer [--two-stage]                # inference latency: the RPN stage [and the whole detector]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench_step.py --gpus N   # scene-parallel, RCCL
 
-What is timed (forward + backward + SGD step, `--batch` scenes per GPU):
+What is timed (forward + backward + optimiser step -- SGD unless --optimizer says otherwise --, `--batch` scenes per GPU):
   RPN backbone   4 SA-MSG levels 16384>4096>1024>256>64 + 4 FP levels (lib/net/pointnet2_msg.py:126-196, point stream) and
                  the cls / reg heads (lib/net/rpn.py:23-52)
   proposals      ProposalLayer (decode, distance-based NMS, 512 proposals per scene)
@@ -286,6 +286,10 @@ def main():
     ap.add_argument("--targets", default="host", choices=["host", "fused"],
                     help="the RCNN target layer: the draw-for-draw restatement of the reference's host random streams (two read-backs "
                          "per step, default) or the sync-free epnet_amd.rcnn_target_layer.RCNNTargetLayer (device tables, two calls)")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "composed", "fused"],
+                    help="how the step ends: torch.optim.SGD with a fixed learning rate (default), the reference's adam_onecycle step "
+                         "composed from stock torch calls (clip_grad_norm_, host one-cycle schedule, per-parameter decay, Adam: "
+                         "bench_ops.ComposedAdamOneCycle), or epnet_amd.optim.FusedAdamOneCycle (three launches, no host scalar)")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without a torch.distributed.run environment the ranks are started as child processes")
     ap.add_argument("--launch-check", action="store_true", help="rehearse the N-rank launch only (see bench.py)")
@@ -327,7 +331,18 @@ def main():
     model = build_model(image=args.image, sampler=args.sampler, loss=args.loss).to(device)
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local], find_unused_parameters=False)
-    opt = torch.optim.SGD(model.parameters(), lr=1e-4, momentum=0.9)
+    total_steps = args.warmup + args.steps + 8                         # the instrumented pass takes up to 5 more
+    if args.optimizer == "fused":
+        from epnet_amd import optim
+        opt = optim.FusedAdamOneCycle(model.module if hasattr(model, "module") else model, total_steps)
+        zero_grad = opt.zero_grad                                      # nothing to do: the step leaves the gradients zero, in place
+    elif args.optimizer == "composed":
+        from bench_ops import ComposedAdamOneCycle
+        opt = ComposedAdamOneCycle(model.parameters(), total_steps)
+        zero_grad = opt.zero_grad
+    else:
+        opt = torch.optim.SGD(model.parameters(), lr=1e-4, momentum=0.9)
+        zero_grad = lambda: opt.zero_grad(set_to_none=True)            # noqa: E731
     if args.targets == "fused":
         from epnet_amd import rcnn_target_layer as rtl
         layers = (pl.ProposalLayer("TRAIN").to(device), rtl.RCNNTargetLayer())
@@ -356,7 +371,7 @@ def main():
             e = torch.cuda.Event(enable_timing=True)
             e.record()
             events.append((name, e))
-        opt.zero_grad(set_to_none=True)
+        zero_grad()
         loss, out = run_step(model, layers, xyz, gts, mark if timed else None, image, xy, args.rpn_only)
         if timed:                                              # the line carries the terms of the last TIMED step
             last_out.update({k: v for k, v in out.items() if k in ("rpn_loss", "rcnn_loss")})
@@ -469,6 +484,8 @@ def main():
                           "per_rank_ms_per_step": {"min": min(r_["ms_per_step"] for r_ in per_rank),
                                                    "max": max(r_["ms_per_step"] for r_ in per_rank)},
                           "loss": last, "data": "synthetic", "dtype": "f32",
+                          **({} if args.optimizer == "sgd" else {"optimizer": args.optimizer}),
+                          **({} if args.optimizer != "fused" else {"optimizer_stats": dict(zip(optim.optim_cuda.STATS_NAMES, opt.stats.tolist()))}),
                           **({} if args.loss == "placeholder" else {"loss_mode": args.loss, "loss_terms": {
                               n_: round(float(v), 6) for r_ in last_out.values() for n_, v in zip(r_.names, r_.terms.tolist())}}),
                           "note": "phase_ms from HIP events (%s); "

@@ -103,6 +103,9 @@ SIGNATURES = {
     "epnet_box_loss_workspace_bytes": (_sz, [ctypes.c_longlong, _i]),
     "epnet_box_loss": (_i, [ctypes.c_longlong, _i, _d, _d, _i, _i, _i, _i, _d, _d, _d, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "epnet_adam_onecycle_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "epnet_adam_onecycle_step": (_i, [_i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _d, _d, _d, _i, _vp, _vp,
+                                      _vp, _vp, _vp, _sz, _vp]),
     "epnet_rpn_targets": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_kitti_overlaps": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_kitti_match": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -76,7 +76,11 @@ def install_callers(sync_free=False):
     that module is loaded (same attribute names), their own yaml-valued defaults otherwise. The default target layer is the
     draw-for-draw restatement of the reference's host random streams; sync_free=True serves
     ``rcnn_target_layer.RCNNTargetLayer`` (same distributions, device tables, no host synchronisation) under the reference's
-    class name instead"""
+    class name instead.
+
+    The optimiser is not served under a module path: tools/train_rcnn.py builds it inline. ``create_optimizer(model)`` +
+    ``create_scheduler(optimizer, total_steps, last_epoch)`` with TRAIN.OPTIMIZER adam_onecycle map onto
+    ``fused_adam_onecycle(model, cfg, total_steps)`` below, and train_utils.py:126-136 onto its ``step()``"""
     install_extensions()
     for dotted, local in _CALLERS.items():
         _ensure_package(dotted)
@@ -89,6 +93,18 @@ def install_callers(sync_free=False):
         sys.modules[dotted] = mod
         parent, leaf = dotted.rsplit(".", 1)
         setattr(sys.modules[parent], leaf, mod)
+
+
+def fused_adam_onecycle(model, cfg, total_steps, **kwargs):
+    """``epnet_amd.optim.FusedAdamOneCycle`` from the reference's ``cfg.TRAIN`` (LR, MOMS, DIV_FACTOR, PCT_START, WEIGHT_DECAY,
+    GRAD_NORM_CLIP; Adam's beta2 = 0.99 is tools/train_rcnn.py:110's). It takes the place of create_optimizer + create_scheduler
+    (tools/train_rcnn.py:98-146) for TRAIN.OPTIMIZER adam_onecycle, and its ``step()`` the place of clip_grad_norm_ +
+    lr_scheduler.step(it) + optimizer.step() in the trainer (train_utils.py:126-136, :186-187). Freeze the RPN (RPN.FIXED)
+    AFTER this call, as the reference does: the state dict then keeps the reference's parameter order."""
+    from . import optim
+    t = cfg.TRAIN
+    return optim.FusedAdamOneCycle(model, total_steps, lr_max=t.LR, moms=tuple(t.MOMS), div_factor=t.DIV_FACTOR, pct_start=t.PCT_START,
+                                   wd=t.WEIGHT_DECAY, grad_norm_clip=t.GRAD_NORM_CLIP, **kwargs)
 
 
 _EVALUATOR = "tools.kitti_object_eval_python"

@@ -694,6 +694,59 @@ int epnet_kitti_pr(int frames, int total_gt, int total_dt, int max_gt, int max_d
                    const double *dt_alpha, const double *thresholds, void *workspace, size_t workspace_bytes,
                    int *pr_counts, double *pr_similarity, epnet_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * the optimiser step (tools/train_utils/train_utils.py:126-136: clip_grad_norm_, then fastai_optim.py:132-149 OptimWrapper.step
+ * with true_wd and bn_wd over torch.optim.Adam, under learning_schedules_fastai.py:40-73 OneCycle)
+ * -------------------------------------------------------------------------------------- */
+
+/* One `adam_onecycle` training step over any number of tensors in three launches (norm partials, finish, update), with no host
+ * synchronisation and no host-side scalar: the step index comes from a device counter and everything that depends on it from a
+ * row table built once, so a captured graph replays the step with a new learning rate every time. The reference sets lr and
+ * beta1 as Python floats per iteration, reads one .item() per parameter in the clip and launches one decay per tensor.
+ *   tensor_table (tensors): where each tensor is; grad NULL = no gradient this step; state_offset = its first element in
+ *     exp_avg / exp_avg_sq (two flat fp32 buffers of the caller's; a multiple of 4 keeps the 16-byte path). Frozen parameters
+ *     are simply not in the table.
+ *   chunk_table (chunks, 2) i32: (tensor, first element); chunk c covers min(EPNET_OPTIM_CHUNK, numel - first) elements of its
+ *     tensor. Every element of every tensor belongs to exactly one chunk; one workgroup per chunk.
+ *   rows (total_steps, EPNET_OPTIM_ROW) fp32, for step t = 0 .. total_steps-1, computed in double and rounded once:
+ *     [decay = 1 - wd lr, b1 = mom, 1 - b1, step_size = lr / (1 - b1^(t+1)), bc2_sqrt = sqrt(1 - b2^(t+1)), lr, mom, 0] with
+ *     lr[t], mom[t] the one-cycle schedule. The device evaluates no cos and no pow: the host's numbers are the definition.
+ *   counter (1) i64: t is read from it and t + 1 written back. t >= total_steps uses the last row and sets the flag in stats
+ *     (the reference's scheduler would run past the cosine's end; its trainer never gets there).
+ * Clip: total_norm = sqrt of the sum of g^2 over every gradient present, in double (one partial per chunk, then the partials
+ * in an order that depends on `chunks` alone; no float atomics: same inputs, same bits); coef = min(1, clip / (total_norm +
+ * 1e-6)) in double, rounded to fp32. A partial does not depend on the gradient's alignment.
+ * Update, per element, fp32 in source order without contraction, / and sqrt correctly rounded:
+ *     g' = g coef;  p = p decay;  m = m b1 + (1 - b1) g';  v = v b2 + (1 - b2) g' g';
+ *     p = p - step_size (m / (sqrt(v) / bc2_sqrt + eps))
+ * (b2, 1 - b2 and eps rounded to fp32 from the doubles given) -- torch.optim.Adam's present form, eps outside the bias
+ * correction, after the wrapper's p *= 1 - wd lr. A tensor without a gradient only decays; its state is not touched.
+ * With zero_grads != 0 every gradient present is stored as zeros afterwards (the buffers persist, their addresses stay).
+ * Full chunks whose p, m, v addresses are multiples of 16 move 16 bytes per lane and access; so does g where its address allows,
+ * else (a gradient that is a view at an odd offset of a bucket) g alone is read and zeroed in dword accesses. A short chunk (a
+ * small tensor, a tensor's last piece) or a parameter at an odd address goes element by element.
+ *   stats (EPNET_OPTIM_STATS) f64: total_norm, coef, lr, mom (the row's fp32 values), the step used, 1 if t >= total_steps,
+ *     then zeros.
+ *   workspace: 16-byte aligned, epnet_adam_onecycle_workspace_bytes(chunks) = 64 + 8 chunks bytes (0 for chunks <= 0).
+ * max_numel: the largest numel in the table (the table lives on the device); above 2^31-1: EPNET_ELIMIT. A NULL required
+ * pointer, total_steps < 1, clip not > 0, eps < 0 or b2 outside [0, 1): EPNET_EINVAL; a missing or short workspace:
+ * EPNET_ENOMEM; tensors == 0 or chunks == 0 returns EPNET_OK and writes nothing (the counter stays).
+ * PRECONDITION: no tensor appears twice, and no parameter, gradient or state range overlaps another. */
+#define EPNET_OPTIM_CHUNK 4096
+#define EPNET_OPTIM_ROW 8
+#define EPNET_OPTIM_STATS 8
+typedef struct {
+    float *param;
+    float *grad;
+    long long numel;
+    long long state_offset;
+} epnet_optim_tensor;
+size_t epnet_adam_onecycle_workspace_bytes(long long chunks);
+int epnet_adam_onecycle_step(int tensors, long long chunks, long long max_numel, const epnet_optim_tensor *tensor_table,
+                             const int *chunk_table, const float *rows, long long total_steps, double clip, double eps,
+                             double b2, int zero_grads, long long *counter, float *exp_avg, float *exp_avg_sq,
+                             double *stats, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
