@@ -130,9 +130,18 @@ template <int W, int PPT>
 __global__ __launch_bounds__(64 * W) void fps_wave_kernel(int n, int m, int lg_bs, const float *__restrict__ xyz,
                                                           float *__restrict__ temp, int *__restrict__ idxs,
                                                           const int *__restrict__ skip, int *__restrict__ prefix_out = nullptr,
-                                                          int prologue_init = -1) {
+                                                          int prologue_init = -1, float *__restrict__ new_xyz = nullptr) {
+    // new_xyz (or NULL): the centres xyz[idx] (b, m, 3), written here behind the indices -- the scene is in the cache, and a
+    // gather of its own behind this kernel is a dispatch more on the sampling chain (see gather_centres4_kernel)
+    if (new_xyz) new_xyz += (size_t)blockIdx.x * m * 3;
     // this scene's first m points are the samples already?
-    if (fps_prologue(m, skip, idxs + (size_t)blockIdx.x * m, prefix_out, prologue_init)) return;
+    if (fps_prologue(m, skip, idxs + (size_t)blockIdx.x * m, prefix_out, prologue_init)) {
+        if (new_xyz) {
+            const float *src = xyz + (size_t)blockIdx.x * n * 3;   // (known prefixes come with m <= n)
+            for (int e = threadIdx.x; e < m * 3; e += blockDim.x) new_xyz[e] = src[e];
+        }
+        return;
+    }
     __shared__ int s_val[2][16];     // per-wave maximum (bit pattern)
     __shared__ float4 s_rec[2][16];  // per-wave candidate: x, y, z, (q << 8 | slot) as int bits
     __shared__ int s_idx[kIdxBuf];
@@ -234,7 +243,14 @@ __global__ __launch_bounds__(64 * W) void fps_wave_kernel(int n, int m, int lg_b
             const int base = it - (kIdxBuf - 1);
             for (int e = lane; e < kIdxBuf; e += 64) {
                 const int c = s_idx[e];
-                idxs[base + e] = fps_point_of(c >> 8, c & 0xFF, R, J, lg_bs);
+                const int k = fps_point_of(c >> 8, c & 0xFF, R, J, lg_bs);
+                idxs[base + e] = k;
+                if (new_xyz) {
+                    float *dst = new_xyz + (size_t)(base + e) * 3;
+                    dst[0] = xyz[k * 3 + 0];
+                    dst[1] = xyz[k * 3 + 1];
+                    dst[2] = xyz[k * 3 + 2];
+                }
             }
         }
     }
@@ -242,7 +258,14 @@ __global__ __launch_bounds__(64 * W) void fps_wave_kernel(int n, int m, int lg_b
         const int base = (m - 1) & ~(kIdxBuf - 1);
         for (int e = lane; base + e < m; e += 64) {
             const int c = s_idx[e];
-            idxs[base + e] = fps_point_of(c >> 8, c & 0xFF, R, J, lg_bs);
+            const int k = fps_point_of(c >> 8, c & 0xFF, R, J, lg_bs);
+            idxs[base + e] = k;
+            if (new_xyz) {
+                float *dst = new_xyz + (size_t)(base + e) * 3;
+                dst[0] = xyz[k * 3 + 0];
+                dst[1] = xyz[k * 3 + 1];
+                dst[2] = xyz[k * 3 + 2];
+            }
         }
     }
     if (temp) {
@@ -1053,8 +1076,11 @@ static bool fps_prune_applies(int n, int m) {
 
 // prologue_init >= 0: skip / prefix_out still want their fps_prefix_kernel treatment with that initial value -- folded into the
 // register-resident kernel, launched separately in front of the others
+// new_xyz (or NULL): the centres, for the kernel that writes them itself; *wrote_centres tells whether the one chosen did
 static int fps_plain(int b, int n, int m, const float *xyz, float *temp, int *idx, const int *skip, int *prefix_out,
-                     epnet_stream_t stream, int prefix_cap = 0x7fffffff, int prologue_init = -1) {
+                     epnet_stream_t stream, int prefix_cap = 0x7fffffff, int prologue_init = -1, float *new_xyz = nullptr,
+                     bool *wrote_centres = nullptr) {
+    if (wrote_centres) *wrote_centres = false;
     EPNET_REQUIRE(b >= 0 && n >= 1 && m >= 0);
     if (b == 0 || m == 0) return EPNET_OK;  // the reference kernel returns at once for m <= 0
     EPNET_REQUIRE(xyz && idx);
@@ -1108,7 +1134,8 @@ static int fps_plain(int b, int n, int m, const float *xyz, float *temp, int *id
         if (w >= 1 && w <= bs_ref / 64 && (bs_ref / (64 * w)) * J <= 16) waves = w;
         const int ppt = (bs_ref / (64 * waves)) * J;
 #define EPNET_FPS_LAUNCH(W_, P_) \
-    hipLaunchKernelGGL((fps_wave_kernel<W_, P_>), grid, dim3(64 * W_), 0, s, n, m, lg, xyz, temp, idx, skip, prefix_out, prologue_init)
+    hipLaunchKernelGGL((fps_wave_kernel<W_, P_>), grid, dim3(64 * W_), 0, s, n, m, lg, xyz, temp, idx, skip, prefix_out, prologue_init, \
+                       new_xyz)
 #define EPNET_FPS_PPT(W_)                      \
     do {                                       \
         if (ppt <= 1) EPNET_FPS_LAUNCH(W_, 1); \
@@ -1126,6 +1153,7 @@ static int fps_plain(int b, int n, int m, const float *xyz, float *temp, int *id
         }
 #undef EPNET_FPS_PPT
 #undef EPNET_FPS_LAUNCH
+        if (wrote_centres) *wrote_centres = new_xyz != nullptr;
         return check_launch("furthest_point_sampling");
     }
     // generic path: needs the running distances in memory
@@ -1171,8 +1199,9 @@ __global__ __launch_bounds__(256) void gather_centres_kernel(int n, int m, const
 }
 
 // four centres per thread (one 16-byte load of indices, three 16-byte stores): a twelfth of the waves of the kernel above. The
-// gather sits on the sampling chain behind every level's FPS, and beside the wide kernels of the pipelined stack what a small
-// kernel waits for is wave slots (77 - 118 us for a copy that takes 8 alone)
+// gather sits on the sampling chain behind the FPS of every level above 1024 points (fps_wave_kernel writes its centres itself),
+// and beside the wide kernels of the pipelined stack what a small kernel waits for is wave slots (77 - 118 us for a copy that
+// takes 8 alone)
 __global__ __launch_bounds__(256) void gather_centres4_kernel(int n, int m, const float *__restrict__ xyz,
                                                               const int *__restrict__ idx, float *__restrict__ out) {
     const int bs = blockIdx.y;
@@ -1204,6 +1233,7 @@ static int fps_over_index(int b, int n, int m, const float *xyz, void *index, si
     int rc;
     const bool plain = need == 0 || !index || n <= 1024 || m <= 1 || (n > 16384 && !temp);
     int fold_init = -1;   // >= 0: the known prefixes / the tie-free counts still need their initial treatment (fps_prologue)
+    bool wrote_centres = false;   // by the sampling kernel itself (fps_wave_kernel)
     if (skip || prefix_out) {
         EPNET_REQUIRE(idx && b <= 65535);
         if (prefix_cap < 1) prefix_cap = 0x7fffffff;
@@ -1215,7 +1245,7 @@ static int fps_over_index(int b, int n, int m, const float *xyz, void *index, si
     }
     // n <= 1024: the reference block size (hence the tie-break rank) depends on n; the one-wave kernel handles it
     if (plain) {
-        rc = fps_plain(b, n, m, xyz, temp, idx, skip, prefix_out, (epnet_stream_t)s, prefix_cap, fold_init);
+        rc = fps_plain(b, n, m, xyz, temp, idx, skip, prefix_out, (epnet_stream_t)s, prefix_cap, fold_init, new_xyz, &wrote_centres);
     } else {
         EPNET_REQUIRE(idx);
         if (index_bytes < need) return EPNET_ENOMEM;
@@ -1248,7 +1278,7 @@ static int fps_over_index(int b, int n, int m, const float *xyz, void *index, si
         }
         rc = check_launch("furthest_point_sampling");
     }
-    if (rc || !new_xyz) return rc;
+    if (rc || !new_xyz || wrote_centres) return rc;
     if (m == 0) return EPNET_OK;
     EPNET_REQUIRE(xyz && b <= 65535);
     launch_gather_centres(b, n, m, xyz, idx, new_xyz, s);

@@ -15,6 +15,8 @@
 //             races. Summation order within a row is still unspecified (as it is in the
 //             reference), so gradients are compared to 1e-5, not bit-for-bit.
 
+#include <type_traits>
+
 #include "common.h"
 #include "spatial.h"
 #include "runsum.h"
@@ -94,6 +96,12 @@ __global__ __launch_bounds__(kGThreads) void gather_rows_scalar_kernel(int c, in
 #ifndef EPNET_GATHER_LDS_UNROLL
 #define EPNET_GATHER_LDS_UNROLL 1
 #endif
+// passes served per iteration where a pass is one row group, i.e. four stores per thread (see serve_span). Level 2 of the
+// 256-scene step, the one shape this is for: 1, 2 and 3 give the same step within its spread (2.83 - 2.99 ms over four
+// alternating rounds each); 4 takes the kernel to 62 registers
+#ifndef EPNET_GATHER_ONE_GROUP_PASSES
+#define EPNET_GATHER_ONE_GROUP_PASSES 2
+#endif
 constexpr int kGLdsThreads = EPNET_GATHER_LDS_THREADS;
 // ---- four channel rows interleaved per LDS word ("quad" staging) ----------------------------------------------------
 // [n][4] floats per group of four rows: one 16-byte LDS read then serves four channel rows of one position -- a quarter of
@@ -116,19 +124,131 @@ __device__ __forceinline__ void stage_quads(const float *__restrict__ src, int g
     }
 }
 
-// positions id.x..w of `groups` quad-staged row groups -> four channel rows of 16 bytes each per group
-__device__ __forceinline__ void serve_quads(const float4 *__restrict__ quad, int groups, int n, int4 id, float *__restrict__ dst,
-                                            int p) {
+// the positions at LDS byte offsets o.x..w of one quad-staged row group -> four channel rows of 16 bytes each
+__device__ __forceinline__ void serve_quad_group(const char *__restrict__ quad, int4 o, float *__restrict__ dst, int p) {
+    const float4 v0 = *reinterpret_cast<const float4 *>(quad + o.x), v1 = *reinterpret_cast<const float4 *>(quad + o.y),
+                 v2 = *reinterpret_cast<const float4 *>(quad + o.z), v3 = *reinterpret_cast<const float4 *>(quad + o.w);
+    store_stream(dst, v0.x, v1.x, v2.x, v3.x);
+    store_stream(dst + p, v0.y, v1.y, v2.y, v3.y);
+    store_stream(dst + 2 * (size_t)p, v0.z, v1.z, v2.z, v3.z);
+    store_stream(dst + 3 * (size_t)p, v0.w, v1.w, v2.w, v3.w);
+}
+
+// the staged rows at byte offsets o.x..w (of the first row or row group) -> out. G > 0: G quad-staged row groups, unrolled,
+// so that the stores behind an index load are a compile-time count (see serve_span); the scheduling barrier keeps a group's
+// four LDS reads from being issued under the group's before, as EPNET_GATHER_LDS_UNROLL explains. G == 0: any number of
+// rows or groups, in a loop.
+template <bool QUAD, int G>
+__device__ __forceinline__ void serve_vector(const float *__restrict__ s_rows, int nr, int n, int4 o, float *__restrict__ dst,
+                                             int p) {
+    const char *row = reinterpret_cast<const char *>(s_rows);
+    if (QUAD) {
+        if (G > 0) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                serve_quad_group(row, o, dst, p);
+                row += (size_t)n * 16;
+                dst += 4 * (size_t)p;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
 #pragma unroll 1
-    for (int g = 0; g < groups; ++g) {
-        const float4 v0 = quad[id.x], v1 = quad[id.y], v2 = quad[id.z], v3 = quad[id.w];
-        store_stream(dst, v0.x, v1.x, v2.x, v3.x);
-        store_stream(dst + p, v0.y, v1.y, v2.y, v3.y);
-        store_stream(dst + 2 * (size_t)p, v0.z, v1.z, v2.z, v3.z);
-        store_stream(dst + 3 * (size_t)p, v0.w, v1.w, v2.w, v3.w);
-        quad += n;
-        dst += 4 * (size_t)p;
+            for (int g = 0; g < (nr >> 2); ++g) {
+                serve_quad_group(row, o, dst, p);
+                row += (size_t)n * 16;
+                dst += 4 * (size_t)p;
+            }
+        }
+        return;
     }
+#pragma unroll EPNET_GATHER_LDS_UNROLL
+    for (int r = 0; r < nr; ++r) {
+        float4 v;
+        v.x = *reinterpret_cast<const float *>(row + o.x);
+        v.y = *reinterpret_cast<const float *>(row + o.y);
+        v.z = *reinterpret_cast<const float *>(row + o.z);
+        v.w = *reinterpret_cast<const float *>(row + o.w);
+        store_stream(dst, v.x, v.y, v.z, v.w);
+        row += (size_t)n * 4;
+        dst += p;
+    }
+}
+
+// the index vector at q + ahead, or the span's last one where q lies behind it. Unconditional on purpose: a load under a condition is
+// sunk into its branch and waited for on the spot with vmcnt(0), which also waits for every store in flight; the clamped
+// address stays inside the scene's index row and its vector is dropped
+__device__ __forceinline__ int4 load_ids(const int *__restrict__ ix, int q, int ahead, int q_last) {
+    return *reinterpret_cast<const int4 *>(ix + (min(q, q_last - ahead) + ahead));   // min(q + ahead, q_last), q + ahead may overflow
+}
+
+// positions -> byte offsets into the staged rows, and the place where a loaded index vector is waited for: the empty asm pins
+// the offsets to registers HERE. Without it the compiler merges the shifts of the prologue and of the loop's end into one at
+// the top of the loop body, and the wait with them (see serve_span)
+template <bool QUAD>
+__device__ __forceinline__ int4 lds_offsets(int4 id) {
+    constexpr int kShift = QUAD ? 4 : 2;
+    int4 o = make_int4(id.x << kShift, id.y << kShift, id.z << kShift, id.w << kShift);
+    asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(o.w));
+    return o;
+}
+
+// The serving loop of both staged gathers: positions [q_begin, q_end) of one index row, kGLdsThreads * 4 of them per pass.
+// Stores count in vmcnt like loads, so "load the indices, wait, serve" waits for every store of the pass before as well, and
+// a wave never has more than one pass of stores in flight. Here the vector of the next pass is loaded BEFORE the current pass
+// is served, and turned into LDS offsets -- its first use -- behind that pass: the wait for it is a counted vmcnt(k), k = the
+// stores of one pass, and those stay in flight into the next pass. The first use sits at the END of the iteration on
+// purpose: a wait at the top of the loop body is sized for the entry from the prologue, where nothing but the next load is
+// behind the vector, and would drain the stores all the same. U > 1 serves U passes per iteration while whole iterations
+// remain -- for shapes whose pass is a single row group, i.e. four stores; the rest of the span, its partial last pass
+// included, goes one pass at a time. q_begin, q_end: multiples of 4, q_end - q_begin >= 4.
+template <bool QUAD, int G, int U>
+__device__ __forceinline__ void serve_span(const float *__restrict__ s_rows, int nr, int n, const int *__restrict__ ix,
+                                           int q_begin, int q_end, float *__restrict__ dst_base, int p) {
+    constexpr int kStep = kGLdsThreads * 4;
+    const int q_last = q_end - 4;
+    int q = q_begin + threadIdx.x * 4;
+    int4 o[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) o[u] = load_ids(ix, q, u * kStep, q_last);
+#pragma unroll
+    for (int u = 0; u < U; ++u) o[u] = lds_offsets<QUAD>(o[u]);
+    if (U > 1) {
+#pragma unroll 1
+        for (int k = (q_end - q_begin) / (U * kStep); k > 0; --k) {   // whole iterations: no thread is out of range
+            int4 nx[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) nx[u] = load_ids(ix, q, (U + u) * kStep, q_last);
+#pragma unroll
+            for (int u = 0; u < U; ++u) serve_vector<QUAD, G>(s_rows, nr, n, o[u], dst_base + q + u * kStep, p);
+#pragma unroll
+            for (int u = 0; u < U; ++u) o[u] = lds_offsets<QUAD>(nx[u]);
+            q += U * kStep;
+        }
+    }
+    int4 cur = o[0];
+#pragma unroll 1
+    for (; q < q_end; q += kStep) {
+        const int4 nx = load_ids(ix, q, kStep, q_last);
+        serve_vector<QUAD, G>(s_rows, nr, n, cur, dst_base + q, p);
+        cur = lds_offsets<QUAD>(nx);
+    }
+}
+
+// the row-group counts of the three shapes the SA stack runs get their compile-time serving loop, every other count the
+// generic one. serve(G, U) is called with the two as integral constants. The caller puts ALL its per-thread work inside
+// `serve`: what four variants share across a loop around them, they also keep alive in registers for one another.
+template <int V>
+using gather_const = std::integral_constant<int, V>;
+template <bool QUAD, typename Serve>
+__device__ __forceinline__ void for_row_groups(int nr, Serve serve) {
+    if (QUAD && nr == 4)
+        serve(gather_const<1>(), gather_const<EPNET_GATHER_ONE_GROUP_PASSES>());
+    else if (QUAD && nr == 16)
+        serve(gather_const<4>(), gather_const<1>());
+    else if (QUAD && nr == 32)
+        serve(gather_const<8>(), gather_const<1>());
+    else
+        serve(gather_const<0>(), gather_const<1>());
 }
 
 template <bool QUAD>  // QUAD: rows % 4 == 0 == c % 4 == n % 4, points 16-byte aligned
@@ -157,31 +277,12 @@ __global__ __launch_bounds__(kGLdsThreads) void gather_rows_lds_kernel(int c, in
     const int q_begin = wg_x * tile, q_end = min(p, q_begin + tile);
     const int *ix = idx + (size_t)bs * p;
     float *dst_base = out + (size_t)bs * ostride + (size_t)c0 * p;
-    for (int q = q_begin + threadIdx.x * 4; q < q_end; q += kGLdsThreads * 4) {
-        const int4 id = *reinterpret_cast<const int4 *>(ix + q);
-        float *dst = dst_base + q;
-        if (QUAD) {
-            serve_quads(reinterpret_cast<const float4 *>(s_rows), nr >> 2, n, id, dst, p);
-            continue;
-        }
-        const float *row = s_rows;
-#pragma unroll EPNET_GATHER_LDS_UNROLL
-        for (int r = 0; r < nr; ++r) {
-            float4 v;
-            v.x = row[id.x];
-            v.y = row[id.y];
-            v.z = row[id.z];
-            v.w = row[id.w];
-            store_stream(dst, v.x, v.y, v.z, v.w);
-            row += n;
-            dst += p;
-        }
-    }
+    if (q_begin >= q_end) return;
+    for_row_groups<QUAD>(nr, [&](auto g, auto u) {
+        serve_span<QUAD, decltype(g)::value, decltype(u)::value>(s_rows, nr, n, ix, q_begin, q_end, dst_base, p);
+    });
 }
 
-#ifndef EPNET_GATHER_LDS2_UNROLL
-#define EPNET_GATHER_LDS2_UNROLL 1   // see EPNET_GATHER_LDS_UNROLL
-#endif
 constexpr long long kGatherLds2MinPositions = 3 * kGLdsThreads * 4;  // both scales together, see epnet_group_concat_multi
 // the same for the TWO scales of an MSG level at once: both gather from the same feature rows, so the rows are
 // staged once and then serve both index sets (saves one 64 KB staging pass per workgroup: 7-12 % of the traffic)
@@ -208,32 +309,15 @@ __global__ __launch_bounds__(kGLdsThreads) void gather_rows_lds2_kernel(int c, i
         for (int e = threadIdx.x; e < total; e += kGLdsThreads) s_rows[e] = src[e];
     }
     __syncthreads();
+    for_row_groups<QUAD>(nr, [&](auto g, auto u) {
 #pragma unroll 1
-    for (int set = 0; set < 2; ++set) {
-        const int p = set ? p1 : p0;
-        const int *ix = (set ? idx1 : idx0) + (size_t)bs * p;
-        float *dst_base = (set ? out1 : out0) + (size_t)bs * (set ? ostride1 : ostride0) + (size_t)c0 * p;
-        for (int q = threadIdx.x * 4; q < p; q += kGLdsThreads * 4) {
-            const int4 id = *reinterpret_cast<const int4 *>(ix + q);
-            float *dst = dst_base + q;
-            if (QUAD) {
-                serve_quads(reinterpret_cast<const float4 *>(s_rows), nr >> 2, n, id, dst, p);
-                continue;
-            }
-            const float *row = s_rows;
-#pragma unroll EPNET_GATHER_LDS2_UNROLL
-            for (int r = 0; r < nr; ++r) {
-                float4 v;
-                v.x = row[id.x];
-                v.y = row[id.y];
-                v.z = row[id.z];
-                v.w = row[id.w];
-                store_stream(dst, v.x, v.y, v.z, v.w);
-                row += n;
-                dst += p;
-            }
+        for (int set = 0; set < 2; ++set) {
+            const int p = set ? p1 : p0;
+            const int *ix = (set ? idx1 : idx0) + (size_t)bs * p;
+            float *dst_base = (set ? out1 : out0) + (size_t)bs * (set ? ostride1 : ostride0) + (size_t)c0 * p;
+            if (p > 0) serve_span<QUAD, decltype(g)::value, decltype(u)::value>(s_rows, nr, n, ix, 0, p, dst_base, p);
         }
-    }
+    });
 }
 
 // scatter-add with the destination rows held in LDS. dynamic LDS: rows * n floats.
