@@ -4,7 +4,7 @@ iou3d (rotated overlap / IoU, both NMS flavours), roipool3d, three_nn / three_in
 gradient ops, at the shapes of the reference's rcnn_online step. One JSON line per op:
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
-    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only]
+    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only]
 """
 import argparse
 import json
@@ -403,6 +403,101 @@ def targets_rows(args, report, timeit_pair):
                % (nbytes / (ms_f * 1e-3) / peak, ms_l, chunk[0], ms_c, ms_c2, agree))
 
 
+def composed_scan_prepare(pts_lidar, num_raw, V2C, R0, P2, img_shape, npoints=16384):
+    """the reference's first half of get_rpn_with_li_fusion (kitti_rcnn_dataset.py:281-356) composed from stock torch on the
+    device, in its shape: a matmul per transform, the masks, then per scene nonzero / randperm with the read-backs their
+    data-dependent sizes force. Its draws are torch's, so only counts and sets can be compared with the fused call."""
+    import torch
+    b, p = pts_lidar.shape[0], pts_lidar.shape[1]
+    hom = torch.cat([pts_lidar[:, :, 0:3], torch.ones_like(pts_lidar[:, :, 0:1])], dim=2)
+    rect = torch.bmm(hom, torch.bmm(V2C.transpose(1, 2), R0.transpose(1, 2)))
+    hom2 = torch.bmm(torch.cat([rect, torch.ones_like(rect[:, :, 0:1])], dim=2), P2.transpose(1, 2))
+    uv = hom2[:, :, 0:2] / rect[:, :, 2:3]
+    depth = hom2[:, :, 2] - P2[:, 2, 3:4]
+    hw = img_shape.to(rect.dtype)
+    flag = (uv[:, :, 0] >= 0) & (uv[:, :, 0] < hw[:, 1:2]) & (uv[:, :, 1] >= 0) & (uv[:, :, 1] < hw[:, 0:1]) & (depth >= 0)
+    flag &= (rect[:, :, 0] >= -40) & (rect[:, :, 0] <= 40) & (rect[:, :, 1] >= -1) & (rect[:, :, 1] <= 3) & (rect[:, :, 2] >= 0) & (rect[:, :, 2] <= 70.4)
+    flag &= torch.arange(p, device=rect.device)[None, :] < num_raw[:, None]
+    out = []
+    for k in range(b):
+        rows = flag[k].nonzero().view(-1)                                    # a read-back: the size depends on the data
+        z = rect[k, rows, 2]
+        if npoints < rows.numel():
+            far, near = (z >= 40.0).nonzero().view(-1), (z < 40.0).nonzero().view(-1)
+            pick = near[torch.randperm(near.numel(), device=rect.device)[:npoints - far.numel()]]
+            choice = torch.cat([pick, far])
+        else:
+            choice = torch.arange(rows.numel(), device=rect.device)
+            if npoints > rows.numel():
+                choice = torch.cat([choice, choice[torch.randperm(rows.numel(), device=rect.device)[:npoints - rows.numel()]]])
+        choice = rows[choice[torch.randperm(choice.numel(), device=rect.device)]]
+        out.append((rect[k, choice], pts_lidar[k, choice, 3] - 0.5, uv[k, choice], choice))
+    return (torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out]), torch.stack([o[2] for o in out]),
+            torch.stack([o[3] for o in out]))
+
+
+def scan_rows(args, report, timeit_pair):
+    """the fused RPN inputs from raw scans (epnet_amd/scan_layer.py, four launches) against composed_scan_prepare, alternating
+    inside one call, at 2 / 16 / 256 scenes of 122 880 raw points -> 16384; and normalise_images against .double() arithmetic
+    plus .float() on the device"""
+    import torch
+    from epnet_amd import scan_layer, synth
+    dev = torch.device("cuda:0")
+    p, n, peak = 122880, 16384, 8e12
+    base = [synth.lidar_scan(p - 1500 * k, seed=60 + k) for k in range(8)]
+    for bsz in (2, 16, 256):
+        pts, num_raw = scan_layer.collate_scans([base[k % 8] for k in range(bsz)])
+        assert pts.shape[1] == p
+        pts, num_raw = pts.to(dev), num_raw.to(dev)
+        cal = [synth.calibration(k % 8) for k in range(bsz)]
+        V2C, R0, P2, shape = (torch.stack([c[j] for c in cal]).to(dev) for j in range(4))
+        tables = scan_layer.draw_scan_tables(bsz, p, n, torch.Generator(device=dev).manual_seed(11), dev)
+
+        def fused():
+            return scan_layer.prepare_scans(pts, num_raw, V2C, R0, P2, shape, tables, npoints=n)
+
+        def fused_fresh_tables():
+            return scan_layer.prepare_scans(pts, num_raw, V2C, R0, P2, shape, scan_layer.draw_scan_tables(bsz, p, n, None, dev), npoints=n)
+
+        def composed():
+            return composed_scan_prepare(pts, num_raw, V2C, R0, P2, shape, n)
+        got, want = fused(), composed()
+        info = got["scene_info"].cpu()
+        # the two draw differently; what must agree: every far point is in both, and both pick valid points only
+        same_far = all(torch.equal(torch.sort(got["choice"][k][got["pts_rect"][k, :, 2] >= 40].long())[0],
+                                   torch.sort(want[3][k][want[0][k, :, 2] >= 40])[0]) for k in range(min(bsz, 4)))
+        if not same_far:
+            print("WARNING: scan_prepare at %d scenes: the fused call and the composition disagree on the far points" % bsz, file=sys.stderr, flush=True)
+        ms_c, ms_f = timeit_pair(composed, fused)
+        ms_c2, ms_t = timeit_pair(composed, fused_fresh_tables)
+        nbytes = bsz * p * 20 + bsz * n * 44
+        report("scan_prepare", {"scenes": bsz, "P": p, "N": n, "valid": info[:4, 1].tolist(), "far": info[:4, 2].tolist(),
+                                "cases": sorted(set(info[:, 3].tolist())), "launches": 4}, ms_f, nbytes,
+               "classify + plan + count + emit, no host sync: %.3f of the 8 TB/s peak over B*P*20 + B*N*44 bytes; with the tables drawn "
+               "in the call (randint + rand + argsort): %.4f ms; stock composition (bmm, masks, per-scene nonzero / randperm with "
+               "read-backs; its launches were not counted, by its statements about 12 + 8 per scene): %.4f ms (%.4f ms in the second pair); same far points in both: %s"
+               % (nbytes / (ms_f * 1e-3) / peak, ms_t, ms_c, ms_c2, same_far))
+    mean, std = torch.tensor(scan_layer.MEAN, dtype=torch.float64, device=dev), torch.tensor(scan_layer.STD, dtype=torch.float64, device=dev)
+    for bsz in (2, 16, 64):
+        img = torch.randint(0, 256, (bsz, 375, 1242, 3), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
+
+        def fused_img():
+            return scan_layer.normalise_images(img)
+
+        def composed_img():
+            back = torch.zeros((bsz, 384, 1280, 3), dtype=torch.float64, device=dev)
+            back[:, :375, :1242] = (img.double() / 255.0 - mean) / std
+            return back.float().permute(0, 3, 1, 2).contiguous()
+        same = bool(torch.equal(fused_img(), composed_img()))
+        if not same:
+            print("WARNING: image_normalise at %d scenes: the fused call and the float64 composition differ" % bsz, file=sys.stderr, flush=True)
+        ms_c, ms_f = timeit_pair(composed_img, fused_img)
+        nbytes = bsz * (375 * 1242 * 3 + 3 * 384 * 1280 * 4)
+        report("image_normalise", {"scenes": bsz, "in": [375, 1242], "out": [384, 1280], "launches": 1}, ms_f, nbytes,
+               "8-bit image -> normalised NCHW fp32, one launch: %.3f of the 8 TB/s peak over the bytes read and written; float64 "
+               "arithmetic on the device + .float() + permute: %.4f ms; same bits: %s" % (nbytes / (ms_f * 1e-3) / peak, ms_c, same))
+
+
 def rcnn_targets_rows(args, report, timeit_pair):
     """the sync-free RCNN target layer (epnet_amd/rcnn_target_layer.py: epnet_rcnn_sample_rois + epnet_roipool3d_train, device
     tables) against the existing ProposalTargetLayer (host random streams, two read-backs), alternating inside one call, at
@@ -493,6 +588,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--loss-only", action="store_true", help="only the training-loss rows (fused against the two stock-torch forms)")
     ap.add_argument("--targets-only", action="store_true", help="only the RPN training targets (fused against bench_step.rpn_labels)")
+    ap.add_argument("--scan-only", action="store_true",
+                    help="only the RPN inputs from raw scans (fused scan_layer.prepare_scans against composed_scan_prepare) and the image normalisation")
     ap.add_argument("--rcnn-targets-only", action="store_true",
                     help="only the RCNN training targets (the sync-free RCNNTargetLayer against the existing ProposalTargetLayer)")
     ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
@@ -625,6 +722,8 @@ def main():
         return targets_rows(args, report, timeit_pair)
     if args.rcnn_targets_only:
         return rcnn_targets_rows(args, report, timeit_pair)
+    if args.scan_only:
+        return scan_rows(args, report, timeit_pair)
     # ---- NMS at the proposal-layer sizes (RPN.NMS_TYPE normal, N <= 6300 / 2700, thresh 0.85) and eval rotated NMS
     for n, rot, thr in ((6300, False, 0.85), (2700, False, 0.85), (6300, True, 0.8), (512, True, 0.1), (100, True, 0.1)):
         boxes, scores = synth.proposal_boxes(n, seed=n, num_objects=40, jitter=1.5)

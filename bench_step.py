@@ -290,6 +290,10 @@ def main():
                     help="how the step ends: torch.optim.SGD with a fixed learning rate (default), the reference's adam_onecycle step "
                          "composed from stock torch calls (clip_grad_norm_, host one-cycle schedule, per-parameter decay, Adam: "
                          "bench_ops.ComposedAdamOneCycle), or epnet_amd.optim.FusedAdamOneCycle (three launches, no host scalar)")
+    ap.add_argument("--inputs", default="arrays", choices=["arrays", "raw"],
+                    help="where the step starts: from the (B,N,3) point arrays a loader would hand over (default), or, with --rpn-only, "
+                         "from raw scans (synth.lidar_scan, 122 880 points each) through scan_layer.prepare_scans and "
+                         "rpn_target_layer.augment_and_label on the device, fresh draws every step, no host synchronisation")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without a torch.distributed.run environment the ranks are started as child processes")
     ap.add_argument("--launch-check", action="store_true", help="rehearse the N-rank launch only (see bench.py)")
@@ -298,6 +302,8 @@ def main():
     args = ap.parse_args()
     if args.two_stage and not args.infer:
         ap.error("--two-stage belongs to --infer")
+    if args.inputs == "raw" and (not args.rpn_only or args.image or args.infer):
+        ap.error("--inputs raw starts the point-stream RPN step (--rpn-only, without --image) from raw scans")
     if args.infer and args.image:
         ap.error("--infer times the point-stream RPN stage; the two-stream backbone (--image) is timed by the training step only")
     from epnet_amd import scene_shard
@@ -357,6 +363,25 @@ def main():
 
     if args.infer:
         return infer(args, model.module if hasattr(model, "module") else model, layers[0], xyz)
+    raw = None
+    if args.inputs == "raw":
+        from epnet_amd import rpn_target_layer, scan_layer, synth
+        scans, num_raw = scan_layer.collate_scans([synth.lidar_scan(122880 - 1500 * k, seed=300 + 1000 * rank + k) for k in range(args.batch)])
+        cal = [synth.calibration(1000 * rank + k) for k in range(args.batch)]
+        raw = {"scans": scans.to(device), "num_raw": num_raw.to(device), "cal": [torch.stack([c[j] for c in cal]).to(device) for j in range(4)],
+               "alpha": torch.zeros(gts.shape[:2], device=device)}
+
+    def step_inputs():
+        """--inputs raw: this step's points from the raw scans, sampled, shuffled and augmented on the device"""
+        if raw is None:
+            return xyz, gts
+        tables = scan_layer.draw_scan_tables(args.batch, raw["scans"].shape[1], args.points, None, device)
+        got = scan_layer.prepare_scans(raw["scans"], raw["num_raw"], *raw["cal"], tables, npoints=args.points)
+        aug = rpn_target_layer.draw_augmentation(args.batch, device=device)
+        pts, boxes, cls_label, reg_label = rpn_target_layer.augment_and_label(got["pts_rect"], gts, raw["alpha"], aug)
+        if args.loss != "placeholder":                     # the labels of THIS step's points
+            (model.module if hasattr(model, "module") else model).rpn_labels = (cls_label, reg_label)
+        return pts, boxes
     if args.loss != "placeholder":
         (model.module if hasattr(model, "module") else model).rpn_labels = rpn_labels(xyz, gts)
 
@@ -372,7 +397,10 @@ def main():
             e.record()
             events.append((name, e))
         zero_grad()
-        loss, out = run_step(model, layers, xyz, gts, mark if timed else None, image, xy, args.rpn_only)
+        step_xyz, step_gts = step_inputs()
+        if raw is not None and timed:
+            mark("inputs")
+        loss, out = run_step(model, layers, step_xyz, step_gts, mark if timed else None, image, xy, args.rpn_only)
         if timed:                                              # the line carries the terms of the last TIMED step
             last_out.update({k: v for k, v in out.items() if k in ("rpn_loss", "rcnn_loss")})
         loss.backward()
@@ -483,7 +511,7 @@ def main():
                           "devices": [r_["device"] for r_ in per_rank], "rehearsal": bool(args.rehearsal),
                           "per_rank_ms_per_step": {"min": min(r_["ms_per_step"] for r_ in per_rank),
                                                    "max": max(r_["ms_per_step"] for r_ in per_rank)},
-                          "loss": last, "data": "synthetic", "dtype": "f32",
+                          "loss": last, "data": "synthetic", "dtype": "f32", **({} if raw is None else {"inputs": "raw"}),
                           **({} if args.optimizer == "sgd" else {"optimizer": args.optimizer}),
                           **({} if args.optimizer != "fused" else {"optimizer_stats": dict(zip(optim.optim_cuda.STATS_NAMES, opt.stats.tolist()))}),
                           **({} if args.loss == "placeholder" else {"loss_mode": args.loss, "loss_terms": {

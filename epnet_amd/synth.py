@@ -112,6 +112,39 @@ def proposal_boxes(num, seed=0, num_objects=40, jitter=1.0):
     return pick.contiguous(), scores
 
 
+def lidar_scan(p, seed=0):
+    """(p,4) [x, y, z, intensity] in the velodyne frame (x forward, y left, z up), as a KITTI .bin scan holds them: ground
+    returns and returns from upright surfaces over the WHOLE azimuth, ranges log-uniform on [3, 80] m, the sensor 1.73 m above
+    the ground, coordinates rounded to 1e-3 m, intensity in [0, 1). Most points fail the camera-view test, as in a real scan
+    (about 120 000 raw points give some 18 000 in view)."""
+    g = _gen(seed + 32452843)
+    u = torch.rand((p, 5), generator=g, dtype=torch.float32)
+    rho = 3.0 * ((80.0 / 3.0) ** u[:, 0])
+    az = (u[:, 1] * 2 - 1) * math.pi
+    ground = u[:, 2] < 0.7
+    z = torch.where(ground, -1.73 + 0.03 * torch.randn((p,), generator=g, dtype=torch.float32), -1.73 + 2.5 * u[:, 3])
+    xyz = torch.stack([rho * torch.cos(az), rho * torch.sin(az), z], dim=1)
+    xyz = torch.round(xyz * 1000.0) / 1000.0
+    return torch.cat([xyz, u[:, 4:5]], dim=1).contiguous()
+
+
+def calibration(seed=0):
+    """KITTI-typical calibration: V2C (3,4), R0 (3,3), P2 (3,4) fp32 and img_shape int32 [h, w] = [375, 1242]; the seed moves
+    the principal point and the mounting by amounts of the size that differ between recording days"""
+    g = _gen(seed + 49979687)
+    d = torch.randn((4,), generator=g, dtype=torch.float64)
+    V2C = torch.tensor([[7.533745e-03, -9.999714e-01, -6.166020e-04, -4.069766e-03],
+                        [1.480249e-02, 7.280733e-04, -9.998902e-01, -7.631618e-02],
+                        [9.998621e-01, 7.523790e-03, 1.480755e-02, -2.717806e-01]], dtype=torch.float64)
+    V2C[:, 3] += 1e-3 * d[0:3]
+    R0 = torch.tensor([[9.999239e-01, 9.837760e-03, -7.445048e-03], [-9.869795e-03, 9.999421e-01, -4.278459e-03],
+                       [7.402527e-03, 4.351614e-03, 9.999631e-01]], dtype=torch.float64)
+    P2 = torch.tensor([[7.215377e+02, 0.0, 6.095593e+02, 4.485728e+01], [0.0, 7.215377e+02, 1.728540e+02, 2.163791e-01],
+                       [0.0, 0.0, 1.0, 2.745884e-03]], dtype=torch.float64)
+    P2[0, 2] += 2.0 * d[3]
+    return V2C.float().contiguous(), R0.float().contiguous(), P2.float().contiguous(), torch.tensor([375, 1242], dtype=torch.int32)
+
+
 def kitti_eval_annos(frames, seed=0, mean_gt=6.0, mean_dt=10.0):
     """(gt_annos, dt_annos) for the AP evaluator (epnet_amd.kitti_eval), as get_label_annos returns them: numpy dicts, not
     tensors -- the evaluator's input is label files. Per frame about mean_gt ground truths (Car / Van / Pedestrian / Cyclist /

@@ -638,6 +638,72 @@ int epnet_rpn_targets(int b, int n, int g, float extra_width, const float *pts, 
                       const float *gt_alpha, const float *aug, float *pts_out, float *gt_out, int *cls_label,
                       float *reg_label, epnet_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * RPN inputs from the raw scans (lib/datasets/kitti_rcnn_dataset.py:281-356, the first half of get_rpn_with_li_fusion:
+ * Calibration.lidar_to_rect / rect_to_img, lib/utils/calibration.py:51-70; get_valid_flag :229-251; the sampling to npoints
+ * :325-346; get_image_rgb_with_normal, lib/datasets/kitti_dataset.py:37-57)
+ * -------------------------------------------------------------------------------------- */
+
+/* The loader's transform, view / scope filter and sampling to n points for a whole batch, with no host synchronisation: the
+ * reference runs them per scene on a host core and draws from numpy's stream; here the draws are device tables, so nothing
+ * is read back. pts_lidar (b,p,4) [x, y, z, intensity] in the velodyne frame, 16-byte aligned, scene k's rows at or beyond
+ * num_raw[k] are padding (num_raw (b) i32 on the device, clamped to [0, p]); V2C (b,3,4), R0 (b,3,3), P2 (b,3,4) f32 the
+ * calibration of each scene; img_shape (b,2) i32 = [h, w]; keys (b,p) i32, compared as UNSIGNED, one draw per raw point;
+ * slot_perm (b,n) i32, a permutation of 0..n-1 per scene, or NULL; scope = 6 doubles in HOST memory [x0, x1, y0, y1, z0, z1]
+ * (PC_AREA_SCOPE row-major; NULL allowed when reduce_by_range == 0), copied at the call; near_depth: the reference's 40.0.
+ * Per raw point, all arithmetic fp32 in source order without contraction, divisions correctly rounded (the conventions of
+ * epnet_kitti_records):
+ *   composite matrix: M[k][j] = (V2C[0][k] * R0[j][0] + V2C[1][k] * R0[j][1]) + V2C[2][k] * R0[j][2], k = 0..3, j = 0..2;
+ *   rectified coordinate: rect_j = ((x * M[0][j] + y * M[1][j]) + z * M[2][j]) + M[3][j], (X, Y, Z) = rect;
+ *   projection: p_r = ((X * P2[r][0] + Y * P2[r][1]) + Z * P2[r][2]) + P2[r][3]; u = p_0 / Z, v = p_1 / Z -- the divisor is
+ *     the rectified Z, not p_2 (calibration.py:68); depth = p_2 - P2[2][3];
+ *   valid: u >= 0 && u < (float)w && v >= 0 && v < (float)h && depth >= 0, and with reduce_by_range != 0 also
+ *     scope[2j] <= (double)rect_j <= scope[2j+1] for j = 0..2, both ends inclusive. The comparison is in double, as numpy
+ *     (NEP 50) compares a float32 array with PC_AREA_SCOPE's float64 entries; legacy value-based casting compared in
+ *     float32 and differs only for a coordinate equal to (float)70.4 (which is above 70.4 and is outside here). A NaN
+ *     anywhere makes the point invalid, and so is every row at or beyond num_raw;
+ *   a valid point is NEAR when Z < near_depth and FAR otherwise.
+ * Selection (:325-346). V = the valid points of the scene, F = the far ones. "The r smallest of a set" means smallest by
+ * (unsigned key, raw index): equal keys go to the lower raw index. The list L has length n: q copies of a forced set S0,
+ * each copy in raw order, then the r smallest of a candidate set S1 in raw order:
+ *   case 0: V > n and F <= n                S0 = far, q = 1          S1 = near, r = n - F
+ *   case 5: F > n (the reference raises)    S0 = none                S1 = far, r = n
+ *   case 1: V == n, case 2: n/2 <= V < n    S0 = valid, q = 1        S1 = valid, r = n - V
+ *   case 3: 0 < V < n/2 (ref. raises)       S0 = valid, q = n div V  S1 = valid, r = n mod V
+ *   case 4: V == 0 (the reference raises)   every output row zero, choice -1
+ * (n/2 is the exact half: case 2 is 2 V >= n.) In cases 0, 1 and 2 uniform keys give the reference's distribution:
+ * np.random.choice(replace = False) is a uniform r-subset, np.random.shuffle is slot_perm. Output row slot_perm[k][j]
+ * receives point L[j] (row j with NULL). PRECONDITION, not checked: slot_perm is a permutation per scene (an entry outside
+ * [0, n) writes nothing, a repeated one leaves a row unwritten). Cost: case 3 writes its q copies of a forced point one
+ * after the other from one lane, O(q) per point (q = n with a single valid point): correct, and slow only on the degenerate
+ * scenes the reference raises on. get_rpn_sample without LI-Fusion is the same rule without
+ * pts_origin_xy and is served by this call.
+ * Outputs, per row: pts_rect (b,n,3) the rectified xyz; pts_intensity (b,n) = intensity - 0.5f; pts_origin_xy (b,n,2) the raw
+ * (u, v) (pointnet2_msg.py:208-210 normalises them later); pts_input (b,n,4) = [xyz, intensity - 0.5] or NULL; choice (b,n) i32
+ * the raw index; scene_info (b,6) i32 = [num_raw clamped, V, F, case, r, q]. Every element of every given output is written.
+ * No float atomics: the bits depend on the inputs alone. Nothing is allocated, nothing synchronises, and the launches are
+ * four whatever the data. PRECONDITION: no output may alias an input or another output. workspace: at least
+ * epnet_scan_prepare_workspace_bytes(b, p, n) bytes, 8-byte aligned, contents irrelevant before and after (too small:
+ * EPNET_ENOMEM). 1 <= n <= 65536, 1 <= p <= 1048576, b <= 65535, else EPNET_ELIMIT before any launch (and 0 from the size
+ * query); b == 0 returns EPNET_OK; a NULL required pointer or a misaligned pts_lidar / workspace: EPNET_EINVAL. */
+size_t epnet_scan_prepare_workspace_bytes(int b, int p, int n);
+int epnet_scan_prepare(int b, int p, int n, int reduce_by_range, const double *scope, float near_depth,
+                       const float *pts_lidar, const int *num_raw, const float *V2C, const float *R0, const float *P2,
+                       const int *img_shape, const int *keys, const int *slot_perm, void *workspace,
+                       size_t workspace_bytes, float *pts_rect, float *pts_intensity, float *pts_origin_xy,
+                       float *pts_input, int *choice, int *scene_info, epnet_stream_t stream);
+
+/* get_image_rgb_with_normal for b scenes from the 8-bit image, in the layout and type the network takes after model_fn's
+ * .float() and permute: img (b,h_in,w_in,3) u8 RGB on the device, out (b,3,h_out,w_out) f32;
+ *   out[k][c][y][x] = (float)((((double)img[k][y][x][c] / 255.0) - mean[c]) / std[c]) for y < min(h_k, h_out), x < min(w_k, w_out),
+ * and 0 elsewhere -- the reference's float64 expression rounded once; h_k, w_k = img_shape[k] ((b,2) i32 = [h, w] on the
+ * device, clamped to [0, h_in] x [0, w_in]) or h_in, w_in with NULL. mean and std are 3 doubles each in HOST memory, copied
+ * at the call. One launch, 16-byte stores when w_out % 4 == 0 and out is 16-byte aligned. Every element of out is written.
+ * b > 65535 or an image of more than 2^31 / 3 pixels: EPNET_ELIMIT; b == 0 returns EPNET_OK. PRECONDITION: out does not
+ * alias img. */
+int epnet_image_normalise(int b, int h_in, int w_in, int h_out, int w_out, const uint8_t *img, const int *img_shape,
+                          const double *mean, const double *std, float *out, epnet_stream_t stream);
+
 /* ---- The KITTI AP evaluator (tools/kitti_object_eval_python: rotate_iou.py:18-296, a numba.cuda kernel, and eval.py:84-332,
  * numba CPU JIT). All frames of a call are ragged: frame f owns rows *_off[f] .. *_off[f+1] of the arrays that go with the
  * offset array (F+1 int32 each) and the dt_num[f] x gt_num[f] float64 block at ov_off[f] (F+1 int64), detection-major as
