@@ -4,7 +4,7 @@ iou3d (rotated overlap / IoU, both NMS flavours), roipool3d, three_nn / three_in
 gradient ops, at the shapes of the reference's rcnn_online step. One JSON line per op:
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
-    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only]
+    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only | --handover-only]
 """
 import argparse
 import json
@@ -498,6 +498,84 @@ def scan_rows(args, report, timeit_pair):
                "arithmetic on the device + .float() + permute: %.4f ms; same bits: %s" % (nbytes / (ms_f * 1e-3) / peak, ms_c, same))
 
 
+def handover_rows(args, report, timeit_pair):
+    """the one-call RPN hand-over (epnet_amd/rpn_handover.py: one decode launch, one order launch, then the proposal kernels)
+    against the existing ProposalLayer.forward (stock decoding and sort in front of the same proposal kernels), alternating inside
+    one call, at 1 / 2 / 16 / 256 scenes x 16384 x 76 with the TRAIN and the TEST budgets; then the two new kernels on their own
+    against the stock ops they replace. The whole table is measured twice: the fused call counts as faster at a size only if its
+    median is below the composition's in both runs AND the gap exceeds the difference between the composition's own two medians.
+    --handover-side runs one side alone (what a kernel trace of launches per call needs)."""
+    import torch
+    from epnet_amd import bbox_transform, proposal_layer, rpn_handover, synth
+    dev = torch.device("cuda:0")
+    n, c, peak = 16384, 76, 8e12
+    cfg = proposal_layer.default_cfg()
+    base = synth.scenes("kitti", 8, n, seed=40)
+    size = torch.from_numpy(cfg.CLS_MEAN_SIZE[0].copy()).to(dev)
+    rows_out = {}
+    sizes = [int(v) for v in args.handover_scenes.split(",")]
+    for run in (1, 2) if args.handover_side == "both" else (1,):
+        for bsz in sizes:
+            gen = torch.Generator(device=dev).manual_seed(41 + bsz)
+            xyz = base[[k % 8 for k in range(bsz)]].contiguous().to(dev)
+            reg = torch.randn((bsz, n, c), generator=gen, device=dev).half().float()
+            scores = torch.randn((bsz, n), generator=gen, device=dev) * 3
+            for mode in ("TRAIN", "TEST"):
+                stock = proposal_layer.ProposalLayer(mode, cfg=cfg).to(dev)
+
+                def composed():
+                    return stock(scores, reg, xyz)
+
+                def composed_all():        # lib/net/point_rcnn.py:44-52 on the existing layer
+                    rois, raw = stock(scores, reg, xyz)
+                    return rois, raw, (torch.sigmoid(scores) > 0.3).float(), torch.norm(xyz, p=2, dim=2)
+
+                def fused():
+                    return rpn_handover.rpn_handover(scores, reg, xyz, cfg=cfg, mode=mode)
+                if args.handover_side != "both":
+                    fn = fused if args.handover_side == "fused" else composed
+                    for _ in range(args.reps):
+                        fn()
+                    torch.cuda.synchronize()
+                    continue
+                got, want = fused(), composed()
+                same_count = bool(torch.equal(got.roi_count, (want[1] != 0).sum(dim=1).int()))
+                ms_c, ms_f = timeit_pair(composed, fused)
+                ms_a, ms_f2 = timeit_pair(composed_all, fused)
+                nbytes = bsz * n * ((c + 4) * 4 + 9 * 4 + 8)
+                rows_out[(bsz, mode, run)] = (ms_c, ms_f)
+                report("rpn_handover", {"scenes": bsz, "N": n, "C": c, "mode": mode, "run": run, "launches": 6}, ms_f, nbytes,
+                       "decode + mask + depth (1 launch), order (1), bin / NMS mask / sweep / emit (4), no host sync; the existing "
+                       "ProposalLayer.forward (stock decoding + torch.sort + the same proposal kernels): %.4f ms; that plus the stock "
+                       "sigmoid / threshold / norm of point_rcnn.py:44-52: %.4f ms against %.4f ms in the same pair; kept counts equal: %s"
+                       % (ms_c, ms_a, ms_f2, same_count))
+            if args.handover_side != "both":
+                continue
+            # the two new kernels on their own
+            flat_xyz, flat_reg = xyz.view(-1, 3), reg.view(-1, c)
+            kw = dict(loc_scope=3.0, loc_bin_size=0.5, num_head_bin=12, get_xz_fine=True, get_y_by_bin=False, get_ry_fine=False,
+                      bbox_avg_by_bin=True, ry_with_bin=False)
+            ms_c, ms_f = timeit_pair(lambda: bbox_transform.decode_bbox_target(flat_xyz, flat_reg, anchor_size=size, **kw),
+                                     lambda: rpn_handover.decode_boxes(flat_xyz, flat_reg, anchor_size=cfg.CLS_MEAN_SIZE[0], **kw))
+            nbytes = bsz * n * ((c + 3) * 4 + 7 * 4)
+            report("decode_bbox_target", {"rows": bsz * n, "C": c, "run": run, "launches": 1}, ms_f, nbytes,
+                   "one launch: %.3f of the 8 TB/s peak over rows * (C + 3 + 7) * 4 bytes; stock bbox_transform.decode_bbox_target: %.4f ms"
+                   % (nbytes / (ms_f * 1e-3) / peak, ms_c))
+            ms_c, ms_f = timeit_pair(lambda: torch.sort(scores, dim=1, descending=True)[1], lambda: rpn_handover.score_order(scores))
+            report("score_order", {"scenes": bsz, "N": n, "run": run, "launches": 1}, ms_f, bsz * n * 12,
+                   "one workgroup per scene, keys sorted in LDS, stable; torch.sort(descending)[1]: %.4f ms" % ms_c)
+    for bsz in sizes:
+        for mode in ("TRAIN", "TEST"):
+            if (bsz, mode, 1) not in rows_out:
+                continue
+            (c1, f1), (c2, f2) = rows_out[(bsz, mode, 1)], rows_out[(bsz, mode, 2)]
+            spread = abs(c1 - c2)
+            faster = f1 < c1 and f2 < c2 and min(c1 - f1, c2 - f2) > spread
+            print(json.dumps({"op": "rpn_handover verdict", "scenes": bsz, "mode": mode, "composed_ms": [round(c1, 4), round(c2, 4)],
+                              "fused_ms": [round(f1, 4), round(f2, 4)], "composed_spread_ms": round(spread, 4), "fused_is_faster": bool(faster)}),
+                  flush=True)
+
+
 def rcnn_targets_rows(args, report, timeit_pair):
     """the sync-free RCNN target layer (epnet_amd/rcnn_target_layer.py: epnet_rcnn_sample_rois + epnet_roipool3d_train, device
     tables) against the existing ProposalTargetLayer (host random streams, two read-backs), alternating inside one call, at
@@ -593,6 +671,11 @@ def main():
     ap.add_argument("--rcnn-targets-only", action="store_true",
                     help="only the RCNN training targets (the sync-free RCNNTargetLayer against the existing ProposalTargetLayer)")
     ap.add_argument("--stage2-only", action="store_true", help="only the second-stage inference pairs (roipool3d_canonical, rcnn_detections)")
+    ap.add_argument("--handover-only", action="store_true",
+                    help="only the RPN hand-over: rpn_handover against the existing ProposalLayer.forward, the whole table twice")
+    ap.add_argument("--handover-side", default="both", choices=["both", "fused", "composed"],
+                    help="with --handover-only: run one side alone, --reps calls per size (what a kernel trace of launches per call needs)")
+    ap.add_argument("--handover-scenes", default="1,2,16,256", help="with --handover-only: the batch sizes, comma separated")
     ap.add_argument("--optim-only", action="store_true",
                     help="only the optimiser step: FusedAdamOneCycle against the stock-torch composition on the two-stream model's parameters")
     ap.add_argument("--optim-side", default="both", choices=["both", "fused", "fused_views", "composed"],
@@ -724,6 +807,8 @@ def main():
         return rcnn_targets_rows(args, report, timeit_pair)
     if args.scan_only:
         return scan_rows(args, report, timeit_pair)
+    if args.handover_only:
+        return handover_rows(args, report, timeit_pair)
     # ---- NMS at the proposal-layer sizes (RPN.NMS_TYPE normal, N <= 6300 / 2700, thresh 0.85) and eval rotated NMS
     for n, rot, thr in ((6300, False, 0.85), (2700, False, 0.85), (6300, True, 0.8), (512, True, 0.1), (100, True, 0.1)):
         boxes, scores = synth.proposal_boxes(n, seed=n, num_objects=40, jitter=1.5)

@@ -6,6 +6,7 @@
     python bench_step.py --image [--gpus N]                   # config 4: the whole rcnn_online step, 62.7 MB of gradients
     python bench_step.py                                      # the point stream alone (round-1 figure)
     python bench_step.py --infer [--two-stage]                # inference latency: the RPN stage [and the whole detector]
+    python bench_step.py --infer --two-stage --proposals fused   # the same with the one-call RPN hand-over (epnet_rpn_handover)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench_step.py --gpus N   # scene-parallel, RCCL
 
 What is timed (forward + backward + optimiser step -- SGD unless --optimizer says otherwise --, `--batch` scenes per GPU):
@@ -45,6 +46,7 @@ SA_MLPS = [[[16, 16, 32], [32, 32, 64]], [[64, 64, 128], [64, 96, 128]], [[128, 
 FP_MLPS = [[128, 128], [256, 256], [512, 512], [512, 512]]
 RCNN_NPOINTS, RCNN_RADIUS, RCNN_NSAMPLE = [128, 32, None], [0.2, 0.4, 100], [64, 64, 64]
 RCNN_MLPS = [[128, 128, 128], [128, 128, 256], [256, 256, 512]]
+PROPOSALS_DEFAULT = "composed"       # --proposals: the stock decoding + sort in front of epnet_rpn_proposals
 
 
 def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder"):
@@ -228,14 +230,15 @@ def infer(args, model, proposal_layer, xyz):
     ms_eager, ms_graph, same, _ = eager_and_graph(stage)
     print(json.dumps({"metric": "RPN-stage inference latency (backbone + heads + proposal layer, eval mode)", "scenes": args.batch,
                       "points_per_scene": args.points, "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3),
-                      "graph_equals_eager": bool(same), "dtype": "f32", "data": "synthetic"}), flush=True)
+                      "graph_equals_eager": bool(same), "proposals": args.proposals, "dtype": "f32", "data": "synthetic"}), flush=True)
     if not args.two_stage:
         return
     # the whole detector (lib/net/point_rcnn.py:33-47 + the eval branch of lib/net/rcnn_net.py:138-164 + tools/eval_rcnn.py:555-583,
     # 663-683): the TEST proposal layer (100 ROIs per scene), canonical ROI pooling, the RCNN stage, decoding + threshold + NMS
     from epnet_amd import detection_layer as dl, proposal_layer as pl
+    fused = args.proposals == "fused"
     test_layer = pl.ProposalLayer("TEST", cfg=proposal_layer.cfg).to(xyz.device)
-    det_layer = dl.DetectionLayer(dl.default_cfg()).to(xyz.device)
+    det_layer = dl.DetectionLayer(dl.default_cfg(), fused_decode=fused).to(xyz.device)
     # the RCNN heads are length-1 convolutions over 100 ROIs per scene: the dense library's default choice for that shape
     # accumulates in an order that changes from run to run (last bits), so two EAGER runs already differ; its deterministic
     # algorithms are asked for here, for the graph == eager comparison to mean something
@@ -244,9 +247,13 @@ def infer(args, model, proposal_layer, xyz):
     def detector():
         with torch.no_grad():
             feats, scores, reg = rpn()
-            rois, _ = test_layer(scores, reg, xyz)
-            seg_mask = (torch.sigmoid(scores) > 0.3).float()
-            depth = torch.norm(xyz, p=2, dim=2)
+            if fused:                                                            # point_rcnn.py:44-52 in one call
+                from epnet_amd import rpn_handover
+                rois, _, seg_mask, depth = rpn_handover.rpn_handover(scores, reg, xyz, cfg=test_layer.cfg, mode="TEST")[:4]
+            else:
+                rois, _ = test_layer(scores, reg, xyz)
+                seg_mask = (torch.sigmoid(scores) > 0.3).float()
+                depth = torch.norm(xyz, p=2, dim=2)
             pts_input, _ = dl.pool_rois(xyz, feats.permute(0, 2, 1).contiguous(), rois, seg_mask, pts_depth=depth, cfg=det_layer.cfg)
             rcnn_cls, rcnn_reg = model.rcnn(pts_input[..., 0:3], pts_input[..., 3:])
             rcnn_cls = rcnn_cls.transpose(1, 2).contiguous().squeeze(dim=1)      # (B*M, 1), lib/net/rcnn_net.py:190
@@ -258,7 +265,8 @@ def infer(args, model, proposal_layer, xyz):
     print(json.dumps({"metric": "two-stage inference latency (RPN stage + ROI pooling + RCNN stage + detections, eval mode)",
                       "scenes": args.batch, "points_per_scene": args.points, "rois_per_scene": int(out[0].shape[1]),
                       "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3), "graph_equals_eager": bool(same),
-                      "detections": counts, "dense_layers_deterministic": True, "dtype": "f32", "data": "synthetic"}), flush=True)
+                      "detections": counts, "dense_layers_deterministic": True, "proposals": args.proposals, "dtype": "f32",
+                      "data": "synthetic"}), flush=True)
 
 
 def main():
@@ -290,6 +298,10 @@ def main():
                     help="how the step ends: torch.optim.SGD with a fixed learning rate (default), the reference's adam_onecycle step "
                          "composed from stock torch calls (clip_grad_norm_, host one-cycle schedule, per-parameter decay, Adam: "
                          "bench_ops.ComposedAdamOneCycle), or epnet_amd.optim.FusedAdamOneCycle (three launches, no host scalar)")
+    ap.add_argument("--proposals", default=PROPOSALS_DEFAULT, choices=["composed", "fused"],
+                    help="between the RPN heads and the proposal kernels: the stock decoding, sort, mask and depth (default) or the "
+                         "one-call hand-over (epnet_amd.rpn_handover: one decode launch, one order launch); the second stage's "
+                         "decoding follows (DetectionLayer(fused_decode=...))")
     ap.add_argument("--inputs", default="arrays", choices=["arrays", "raw"],
                     help="where the step starts: from the (B,N,3) point arrays a loader would hand over (default), or, with --rpn-only, "
                          "from raw scans (synth.lidar_scan, 122 880 points each) through scan_layer.prepare_scans and "
@@ -351,9 +363,9 @@ def main():
         zero_grad = lambda: opt.zero_grad(set_to_none=True)            # noqa: E731
     if args.targets == "fused":
         from epnet_amd import rcnn_target_layer as rtl
-        layers = (pl.ProposalLayer("TRAIN").to(device), rtl.RCNNTargetLayer())
+        layers = (pl.ProposalLayer("TRAIN", fused_head=args.proposals == "fused").to(device), rtl.RCNNTargetLayer())
     else:
-        layers = (pl.ProposalLayer("TRAIN").to(device), ptl.ProposalTargetLayer())
+        layers = (pl.ProposalLayer("TRAIN", fused_head=args.proposals == "fused").to(device), ptl.ProposalTargetLayer())
     xyz, gts = synthetic_batch(args.batch, args.points, 100 + 1000 * rank, device)   # every rank its own scenes
     image = xy = None
     if args.image:

@@ -87,6 +87,11 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_rpn_proposals_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "epnet_rpn_proposals": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "epnet_decode_bbox_target": (_i, [ctypes.c_longlong, _i, _vp, _vp, _i, _i, _i, _d, _d, _d, _d, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "epnet_score_order": (_i, [_i, _i, _vp, _vp, _vp]),
+    "epnet_rpn_handover_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "epnet_rpn_handover": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _d, _d, _d, _d, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _i, _f, _i, _vp,
+                                _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_rcnn_detections_workspace_bytes": (_sz, [_i, _i]),
     "epnet_rcnn_detections": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp]),
     "epnet_eval_recall_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -70,13 +70,14 @@ def install_surface(include_kitti_utils=False):
         setattr(sys.modules[parent], leaf, mod)
 
 
-def install_callers(sync_free=False):
+def install_callers(sync_free=False, fused_head=False):
     """serve this package's ProposalLayer / ProposalTargetLayer under the reference's module paths, so that
     lib/net/rpn.py and lib/net/rcnn_net.py construct them unchanged; both read the reference's ``lib.config.cfg`` when
     that module is loaded (same attribute names), their own yaml-valued defaults otherwise. The default target layer is the
     draw-for-draw restatement of the reference's host random streams; sync_free=True serves
     ``rcnn_target_layer.RCNNTargetLayer`` (same distributions, device tables, no host synchronisation) under the reference's
-    class name instead.
+    class name instead. fused_head=True serves a ProposalLayer whose forward is one ``epnet_rpn_handover`` call (decoding, score
+    order and proposals; rpn_handover.py) under the reference's class name.
 
     The optimiser is not served under a module path: tools/train_rcnn.py builds it inline. ``create_optimizer(model)`` +
     ``create_scheduler(optimizer, total_steps, last_epoch)`` with TRAIN.OPTIMIZER adam_onecycle map onto
@@ -90,6 +91,16 @@ def install_callers(sync_free=False):
             mod = types.ModuleType(dotted)
             mod.__dict__.update({k: v for k, v in vars(fused).items() if not k.startswith("__")})
             mod.ProposalTargetLayer = fused.RCNNTargetLayer
+        if fused_head and local == "proposal_layer":
+            stock = mod
+
+            class ProposalLayer(stock.ProposalLayer):
+                def __init__(self, mode='TRAIN', cfg=None):
+                    super().__init__(mode, cfg, fused_head=True)
+
+            mod = types.ModuleType(dotted)
+            mod.__dict__.update({k: v for k, v in vars(stock).items() if not k.startswith("__")})
+            mod.ProposalLayer = ProposalLayer
         sys.modules[dotted] = mod
         parent, leaf = dotted.rsplit(".", 1)
         setattr(sys.modules[parent], leaf, mod)

@@ -88,6 +88,15 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     return v;
 }
 
+// float -> unsigned, order preserving; -0.0 and +0.0 share a key and so does every NaN (above +inf: torch.sort(descending)
+// puts a NaN first). The key rule of the second-stage detections (iou3d.hip) and of epnet_score_order (handover.hip).
+__device__ __forceinline__ unsigned ordered_key(float v) {
+    if (v != v) return 0xffffffffu;
+    if (v == 0.f) v = 0.f;
+    const unsigned u = (unsigned)__float_as_int(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 }  // namespace epnet
 
 #define EPNET_REQUIRE(cond) \

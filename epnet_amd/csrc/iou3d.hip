@@ -828,14 +828,7 @@ __global__ __launch_bounds__(256) void proposal_emit_kernel(int n, int pre0, int
 constexpr int kDetThreads = 1024;
 constexpr int kDetMaxM = 4096;
 
-// float -> unsigned, order preserving; -0.0 and +0.0 share a key and so does every NaN (above +inf: torch.sort(descending)
-// puts a NaN first)
-__device__ __forceinline__ unsigned ordered_key(float v) {
-    if (v != v) return 0xffffffffu;
-    if (v == 0.f) v = 0.f;
-    const unsigned u = (unsigned)__float_as_int(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// ordered_key (common.h): float -> unsigned, order preserving; it fixes the order of the candidates below
 
 // sel (b, m): ROI index of the candidate at each rank; counts (b): candidates; bev (b, m, 5) in rank order
 __global__ __launch_bounds__(kDetThreads) void det_select_kernel(int m, float score_thresh, const float *__restrict__ boxes3d,

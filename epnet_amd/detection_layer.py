@@ -5,7 +5,8 @@ The reference pools 100 ROIs per scene into a zero-filled tensor, subtracts the 
 scene by scene in a Python loop (cos, sin, three ``cat``, an indexed read, a batched matmul, an indexed write -- per scene);
 behind the network it thresholds the scores and walks the scenes again: ``inds[k].sum() == 0`` (a sync), boolean-mask
 indexing (a sync), a sort, an NMS whose mask goes to the host, more indexing, ``.cpu()``. Here ``pool_rois`` is the input
-``cat`` + one launch of ``epnet_roipool3d_canonical`` (csrc/roipool3d.hip) and ``DetectionLayer`` is the decoding, a sigmoid
+``cat`` + one launch of ``epnet_roipool3d_canonical`` (csrc/roipool3d.hip) and ``DetectionLayer`` is the decoding (stock tensor
+ops, or with ``fused_decode=True`` one launch of ``epnet_decode_bbox_target``, csrc/handover.hip), a sigmoid
 and ``epnet_rcnn_detections`` (csrc/iou3d.hip: select, batched rotated NMS with device-side counts, emit). Nothing is read
 back to the host, so the whole second stage can sit inside a captured HIP graph; the results are padded to M rows per scene
 with a device-side count instead of ragged host arrays.
@@ -63,9 +64,10 @@ def pool_rois(rpn_xyz, rpn_features, roi_boxes3d, seg_mask, pts_depth=None, rpn_
 
 
 class DetectionLayer(nn.Module):
-    def __init__(self, cfg=None):
+    def __init__(self, cfg=None, fused_decode=False):
         super().__init__()
         self.cfg = cfg if cfg is not None else _ambient_cfg()
+        self.fused_decode = bool(fused_decode)
         self.register_buffer("MEAN_SIZE", torch.from_numpy(np.asarray(self.cfg.CLS_MEAN_SIZE[0], dtype=np.float32)), persistent=False)
 
     def forward(self, rois, rcnn_cls, rcnn_reg, rcnn_iou_branch=None):
@@ -83,12 +85,16 @@ class DetectionLayer(nn.Module):
             raise NotImplementedError("RCNN.SIZE_RES_ON_ROI (the reference asserts False, tools/eval_rcnn.py:565-566)")
         if rcnn_cls.shape[2] != 1:
             raise NotImplementedError("a class head wider than 1 (tools/eval_rcnn.py:584-587)")
-        pred_boxes3d = decode_bbox_target(rois.reshape(-1, 7), rcnn_reg.reshape(-1, rcnn_reg.shape[-1]), anchor_size=self.MEAN_SIZE,
-                                          loc_scope=rcnn.LOC_SCOPE, loc_bin_size=rcnn.LOC_BIN_SIZE, num_head_bin=rcnn.NUM_HEAD_BIN,
-                                          get_xz_fine=True, get_y_by_bin=rcnn.LOC_Y_BY_BIN, loc_y_scope=rcnn.LOC_Y_SCOPE,
-                                          loc_y_bin_size=rcnn.LOC_Y_BIN_SIZE, get_ry_fine=True,
-                                          bbox_avg_by_bin=self.cfg.TRAIN.BBOX_AVG_BY_BIN,
-                                          ry_with_bin=self.cfg.TEST.RY_WITH_BIN).view(batch_size, -1, 7)  # :568-575
+        if self.fused_decode:
+            from .rpn_handover import decode_boxes
+            decode, anchor_size = decode_boxes, np.asarray(self.cfg.CLS_MEAN_SIZE[0], dtype=np.float32)   # host numbers: no read-back
+        else:
+            decode, anchor_size = decode_bbox_target, self.MEAN_SIZE
+        pred_boxes3d = decode(rois.reshape(-1, 7), rcnn_reg.reshape(-1, rcnn_reg.shape[-1]), anchor_size=anchor_size,
+                              loc_scope=rcnn.LOC_SCOPE, loc_bin_size=rcnn.LOC_BIN_SIZE, num_head_bin=rcnn.NUM_HEAD_BIN,
+                              get_xz_fine=True, get_y_by_bin=rcnn.LOC_Y_BY_BIN, loc_y_scope=rcnn.LOC_Y_SCOPE,
+                              loc_y_bin_size=rcnn.LOC_Y_BIN_SIZE, get_ry_fine=True, bbox_avg_by_bin=self.cfg.TRAIN.BBOX_AVG_BY_BIN,
+                              ry_with_bin=self.cfg.TEST.RY_WITH_BIN).view(batch_size, -1, 7)  # :568-575
         raw_scores = rcnn_cls[:, :, 0].float().contiguous()                              # :579
         norm_scores = torch.sigmoid(raw_scores)                                          # :581
         pred_boxes3d = pred_boxes3d.float().contiguous()

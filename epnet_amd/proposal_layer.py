@@ -8,7 +8,8 @@ the GIL, more slicing, ``torch.cat`` and a copy into the zero-padded result -- a
 scene. Here the decoding and the sort stay stock tensor ops and everything after them is ``epnet_rpn_proposals``
 (csrc/iou3d.hip): bin compaction in score order, one batched NMS (mask + sweep) over all (scene, bin) groups with the
 group sizes read from device memory, and the gather into the padded outputs. Nothing is read back to the host, so the
-layer can sit inside a captured HIP graph.
+layer can sit inside a captured HIP graph. ``ProposalLayer(mode, fused_head=True)`` replaces the stock decoding and sort as
+well: ``forward`` is then one ``epnet_rpn_handover`` call (rpn_handover.py, csrc/handover.hip).
 """
 from types import SimpleNamespace
 
@@ -41,9 +42,10 @@ def _ambient_cfg():
 
 
 class ProposalLayer(nn.Module):
-    def __init__(self, mode='TRAIN', cfg=None):
+    def __init__(self, mode='TRAIN', cfg=None, fused_head=False):
         super().__init__()
         self.mode = mode
+        self.fused_head = bool(fused_head)
         self.cfg = cfg if cfg is not None else _ambient_cfg()
         self.register_buffer("MEAN_SIZE", torch.from_numpy(np.asarray(self.cfg.CLS_MEAN_SIZE[0], dtype=np.float32)), persistent=False)
 
@@ -64,6 +66,15 @@ class ProposalLayer(nn.Module):
     def forward(self, rpn_scores, rpn_reg, xyz):
         """rpn_scores (B,N), rpn_reg (B,N,C), xyz (B,N,3) -> ret_bbox3d (B,M,7), ret_scores (B,M), M = RPN_POST_NMS_TOP_N,
         zero rows behind the kept proposals"""
+        if self.fused_head:
+            from . import handover_cuda, rpn_handover
+            args = rpn_handover.handover_args(self.cfg, self.mode)
+            batch_size, post = rpn_scores.size(0), args["post_nms_top_n"]
+            ret_bbox3d = torch.empty((batch_size, post, 7), dtype=torch.float32, device=rpn_scores.device)
+            ret_scores = torch.empty((batch_size, post), dtype=torch.float32, device=rpn_scores.device)
+            handover_cuda.rpn_handover_gpu(rpn_scores.float().contiguous(), rpn_reg.float().contiguous(), xyz.float().contiguous(),
+                                           ret_bbox3d=ret_bbox3d, ret_scores=ret_scores, **args)
+            return ret_bbox3d, ret_scores
         proposals = self.decode(rpn_reg, xyz).float().contiguous()
         return self.propose(rpn_scores.float().contiguous(), proposals)
 

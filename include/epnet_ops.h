@@ -417,6 +417,55 @@ int epnet_rpn_proposals(int b, int n, const float *proposals, const float *score
                         void *workspace, size_t workspace_bytes, float *ret_bbox3d, float *ret_scores, int *ret_count,
                         epnet_stream_t stream);
 
+/* decode_bbox_target, lib/utils/bbox_transform.py:25-262, in ONE launch, for both stages: anchors (rows, anchor_cols) with
+ * anchor_cols 3 (the RPN's points) or 7 (the RCNN stage's ROIs), pred_reg (rows, channels) with the channel layout
+ * [x bins | z bins | x residuals | z residuals (with xz_fine)] [y offset | y bins, y residuals (with y_by_bin)]
+ * [ry bins | ry residuals] [h, w, l residuals] -> boxes (rows, 7) [x, y, z, h, w, l, ry]. bins_xz and bins_y are the caller's
+ * int(scope / bin_size) * 2 (no float-to-int conversion happens here); anchor_size: 3 floats in HOST memory, copied at the call
+ * (they travel by value in the kernel arguments: the call is graph-capturable). x, z: the soft-max weighted mean of (bin centre +
+ * residual) with avg_by_bin, else the FIRST maximal bin (torch.argmax; a NaN counts as the maximum) plus, with xz_fine, its
+ * residual; y: anchor y + offset, or the arg-max y bin; heading: the arg-max bin -- coarse (ry_fine == 0): the full turn in
+ * num_head_bin bins, taken modulo 2 pi with the sign of the divisor and wrapped into (-pi, pi]; fine: a quarter turn around the
+ * ROI's own heading -- or, with ry_with_bin, the probability-weighted mean over the likelier of the two sides (:146-238); sizes
+ * residual * anchor_size + anchor_size; for 7-wide anchors (x, z) is rotated by -roi_ry and ry += roi_ry; x, z += the anchor's;
+ * with y_to_bottom y += h / 2 (lib/rpn/proposal_layer.py:31). fp32 in source order without contraction. Checked before any
+ * launch: channels == (xz_fine ? 4 : 2) * bins_xz + (y_by_bin ? 2 * bins_y : 1) + 2 * num_head_bin + 3, avg_by_bin only with
+ * xz_fine (the reference asserts), anchor_cols in {3, 7}, a NULL pointer: EPNET_EINVAL; channels > 255: EPNET_ELIMIT;
+ * rows == 0 returns EPNET_OK and writes nothing. PRECONDITION: boxes does not alias an input. */
+int epnet_decode_bbox_target(long long rows, int anchor_cols, const float *anchors, const float *pred_reg, int channels,
+                             int bins_xz, int bins_y, double loc_scope, double loc_bin_size, double loc_y_scope,
+                             double loc_y_bin_size, int num_head_bin, const float *anchor_size, int xz_fine, int y_by_bin,
+                             int ry_fine, int avg_by_bin, int ry_with_bin, int y_to_bottom, float *boxes, epnet_stream_t stream);
+
+/* The per-scene STABLE descending order of scores (b,n) as order (b,n) i64, the layout epnet_rpn_proposals reads, in one
+ * launch of one workgroup per scene (torch.sort, lib/rpn/proposal_layer.py:35, leaves the order of equal scores open). The key
+ * rule is epnet_rcnn_detections': compared as floats, -0.0 == +0.0, a NaN ranks before every number, EQUAL scores in ASCENDING
+ * index. No float atomics: the result depends on the inputs alone. 1 <= n <= 16384 and b <= 65535, else EPNET_ELIMIT before
+ * the launch; b == 0 returns EPNET_OK; a NULL pointer: EPNET_EINVAL. */
+int epnet_score_order(int b, int n, const float *scores, int64_t *order, epnet_stream_t stream);
+
+/* lib/net/point_rcnn.py:44-52 with lib/rpn/proposal_layer.py:23-55 for the whole batch in one call with no host
+ * synchronisation, no allocation and no state: scores (b,n) = rpn_cls[:, :, 0], rpn_reg (b,n,channels), xyz (b,n,3), the decode
+ * parameters of epnet_decode_bbox_target (anchor_cols = 3, y_to_bottom = 1), score_thresh, and epnet_rpn_proposals' parameters.
+ * Launches, fixed by the code whatever the data: ONE that decodes the boxes and writes proposals, seg_mask and pts_depth (scores
+ * and xyz are read once), ONE that orders the scores (epnet_score_order), then epnet_rpn_proposals' own, unchanged: 7 with the
+ * rotated NMS, 6 with the normal one. Results, every element of every given output written: ret_bbox3d (b, post_nms_top_n, 7),
+ * ret_scores (b, post_nms_top_n); optional (NULL allowed): ret_count (b) i32; seg_mask (b,n) = sigmoid(score) > score_thresh as
+ * 1.0 / 0.0 (a NaN score gives 0); pts_depth (b,n) = sqrt(x^2 + y^2 + z^2); proposals (b,n,7) the decoded boxes; order (b,n)
+ * i64. Without a caller's buffer, proposals and order live in the workspace. 1 <= n <= 16384, b <= 32767, channels <= 255, else
+ * EPNET_ELIMIT before any launch; a NULL required pointer, post_nms_top_n < 1 or a channel count that does not fit:
+ * EPNET_EINVAL; a workspace below epnet_rpn_handover_workspace_bytes (pure arithmetic: (b,n,7) floats and (b,n) i64, each
+ * rounded up to 16 bytes, plus epnet_rpn_proposals_workspace_bytes; 0 outside the limits): EPNET_ENOMEM; b == 0 returns EPNET_OK.
+ * PRECONDITION: no output aliases an input. */
+size_t epnet_rpn_handover_workspace_bytes(int b, int n, int distance_based, int pre_nms_top_n, int post_nms_top_n);
+int epnet_rpn_handover(int b, int n, int channels, const float *scores, const float *rpn_reg, const float *xyz, int bins_xz,
+                       int bins_y, double loc_scope, double loc_bin_size, double loc_y_scope, double loc_y_bin_size,
+                       int num_head_bin, const float *anchor_size, int xz_fine, int y_by_bin, int ry_fine, int avg_by_bin,
+                       int ry_with_bin, float score_thresh, int distance_based, int pre_nms_top_n, int post_nms_top_n,
+                       float nms_thresh, int rotated, void *workspace, size_t workspace_bytes, float *ret_bbox3d,
+                       float *ret_scores, int *ret_count, float *seg_mask, float *pts_depth, float *proposals, int64_t *order,
+                       epnet_stream_t stream);
+
 /* The end of eval_one_epoch_joint, tools/eval_rcnn.py:663-683, for all b scenes with no host synchronisation: score
  * threshold, sort, rotated NMS, gather. boxes3d (b,m,7) decoded boxes, raw_scores / norm_scores (b,m). Per scene the
  * candidates are the ROIs with norm_scores > score_thresh (a NaN is never one), ordered by DESCENDING raw_scores compared
