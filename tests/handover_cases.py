@@ -33,7 +33,17 @@ CONFIGS = {
     "rcnn_y_by_bin": dict(_RCNN, get_y_by_bin=True),                        # 53 channels
     "hard_coarse_xz": dict(_RPN, bbox_avg_by_bin=False, get_xz_fine=False),   # 52 channels
     "rcnn_ry_with_bin": dict(_RCNN, ry_with_bin=True),                      # the fine-heading side rule
+    # the ends of the staging loop's (row, column) bookkeeping, dr = 256 / c, dc = 256 - dr * c (the names sort behind the
+    # entries above, whose seeds depend on their place in the sorted list): the fewest channels the argument rules allow
+    # (int(scope / bin) * 2 >= 2 bins per axis, one heading bin), either side of 128, and the two largest (255 = kMaxChannels)
+    "staging_c010": dict(_RPN, loc_scope=0.5, num_head_bin=1, get_xz_fine=False, bbox_avg_by_bin=False),
+    "staging_c128": dict(_RPN, loc_scope=6.0, num_head_bin=14),
+    "staging_c129": dict(_RCNN, loc_scope=6.0, get_y_by_bin=True, loc_y_bin_size=0.5, num_head_bin=13),
+    "staging_c254": dict(_RPN, loc_scope=12.5, num_head_bin=25, bbox_avg_by_bin=False),
+    "staging_c255": dict(_RCNN, loc_scope=12.5, get_y_by_bin=True, loc_y_bin_size=0.5, num_head_bin=24, bbox_avg_by_bin=False),
 }
+STAGING = {"staging_c010": 10, "staging_c128": 128, "staging_c129": 129, "staging_c254": 254, "staging_c255": 255}
+TOO_WIDE = dict(_RPN, loc_scope=12.5, num_head_bin=26)                      # 256 channels: one more than the LDS tile takes
 
 
 def channels(cfg):
