@@ -617,6 +617,98 @@ def rcnn_targets_rows(args, report, timeit_pair):
                % (ms_host, ms_draw, ms_sample, sample_bytes, ms_cat, ms_pool))
 
 
+def rows16_rows(args, timeit_pair):
+    """the native 16-bit kernels (csrc/rows16.hip) against their float32 twins -- unchanged code moving twice the feature bytes --
+    and against the upcast composition (x.float() -> float32 op -> .to(T)), on the SA / FP level shapes of configs 3 and 4 at 2 and
+    16 scenes. Every pair alternates inside one call, median of --reps by HIP events; native against twin twice (two passes)."""
+    import torch
+    from epnet_amd import pointnet2_cuda as p2
+    dev, T, f32, i32 = torch.device("cuda:0"), torch.bfloat16, torch.float32, torch.int32
+    g = torch.Generator(device=dev).manual_seed(0)
+    PEAK = 8.0e12
+
+    def line(op, shape, native, twin, upcast, nbytes, twin_bytes):
+        spread = abs(twin[0] - twin[1])
+        faster_twin = all(n < t - spread for n, t in zip(native, twin))
+        best = min(native)
+        print(json.dumps({"op": op + "_h", "dtype": "bf16", "shape": shape, "ms_native": [round(v, 4) for v in native],
+                          "ms_f32_twin": [round(v, 4) for v in twin], "twin_spread_ms": round(spread, 4), "ms_upcast_composition": round(upcast[1], 4),
+                          "ms_native_beside_upcast": round(upcast[0], 4), "algorithmic_bytes": nbytes, "twin_algorithmic_bytes": twin_bytes,
+                          "share_of_8TBps": round(nbytes / (best * 1e-3) / PEAK, 3), "twin_share_of_8TBps": round(twin_bytes / (min(twin) * 1e-3) / PEAK, 3),
+                          "faster_than_twin": bool(faster_twin), "faster_than_upcast": bool(upcast[0] < upcast[1])}), flush=True)
+
+    for scenes in (2, 16):
+        clouds = scenes * 64                               # ROIs of the RCNN stage
+        # ---- group_linear: (b, c, n, npoint, ns) of the foldable levels (RPN levels 2-4, RCNN levels 1-2)
+        for tag, (b, c, n, m, ns) in (("rpn2/16", (scenes, 64, 4096, 1024, 16)), ("rpn2/32", (scenes, 64, 4096, 1024, 32)),
+                                      ("rpn3/32", (scenes, 128, 1024, 256, 32)), ("rpn4/32", (scenes, 256, 256, 64, 32)),
+                                      ("rcnn1", (clouds, 128, 512, 128, 64)), ("rcnn2", (clouds, 128, 128, 32, 64))):
+            xyz = torch.rand((b, n, 3), generator=g, device=dev)
+            new_xyz = xyz[:, :m].contiguous()
+            idx = torch.randint(0, n, (b, m, ns), generator=g, device=dev, dtype=i32)
+            z32 = torch.randn((b, c, n), generator=g, device=dev)
+            z16 = z32.to(T)
+            w, bias = torch.randn((c, 3), generator=g, device=dev), torch.randn((c,), generator=g, device=dev)
+            o16, o32 = torch.empty((b, c, m, ns), dtype=T, device=dev), torch.empty((b, c, m, ns), dtype=f32, device=dev)
+            native = lambda: p2.group_linear_h_wrapper(b, c, n, m, ns, xyz, new_xyz, z16, idx, w, bias, o16)          # noqa: E731
+            twin = lambda: p2.group_linear_wrapper(b, c, n, m, ns, xyz, new_xyz, z32, idx, w, bias, o32)                # noqa: E731
+
+            def upcast():
+                p2.group_linear_wrapper(b, c, n, m, ns, xyz, new_xyz, z16.float(), idx, w, bias, o32)
+                return o32.to(T)
+            a, bb = timeit_pair(native, twin), timeit_pair(native, twin)
+            per = lambda e: b * (c * n * e + n * 12 + m * 12 + m * ns * 4 + c * m * ns * e)                             # noqa: E731
+            line("group_linear", {"level": tag, "scenes": scenes, "b": b, "c": c, "n": n, "npoint": m, "ns": ns}, (a[0], bb[0]), (a[1], bb[1]),
+                 timeit_pair(native, upcast), per(2), per(4))
+            del z32, z16, o16, o32
+        # ---- pool_max and its gradient: (rows, ns)
+        for tag, (rows, ns) in (("rpn1/16", (scenes * 32 * 4096, 16)), ("rpn1/32", (scenes * 64 * 4096, 32)), ("rpn2/32", (scenes * 128 * 1024, 32)),
+                                ("rcnn1", (clouds * 128 * 128, 64)), ("rcnn3", (clouds * 512, 32))):
+            x32 = torch.randn((rows, ns), generator=g, device=dev)
+            x16 = x32.to(T)
+            o16, o32 = torch.empty((rows,), dtype=T, device=dev), torch.empty((rows,), dtype=f32, device=dev)
+            arg = torch.empty((rows,), dtype=i32, device=dev)
+            native = lambda: p2.pool_max_h_wrapper(rows, ns, x16, o16, arg)            # noqa: E731
+            twin = lambda: p2.pool_max_wrapper(rows, ns, x32, o32, arg)                # noqa: E731
+
+            def upcast():
+                p2.pool_max_wrapper(rows, ns, x16.float(), o32, arg)
+                return o32.to(T)
+            a, bb = timeit_pair(native, twin), timeit_pair(native, twin)
+            line("pool_max", {"level": tag, "scenes": scenes, "rows": rows, "ns": ns}, (a[0], bb[0]), (a[1], bb[1]), timeit_pair(native, upcast),
+                 rows * (ns * 2 + 2 + 4), rows * (ns * 4 + 4 + 4))
+            g16, g32 = torch.randn((rows,), generator=g, device=dev).to(T), torch.randn((rows,), generator=g, device=dev)
+            native = lambda: p2.pool_max_grad_h_wrapper(rows, ns, g16, arg, x16)       # noqa: E731  (x16 / x32 reused as grad_x)
+            twin = lambda: p2.pool_max_grad_wrapper(rows, ns, g32, arg, x32)           # noqa: E731
+
+            def upcast():
+                p2.pool_max_grad_wrapper(rows, ns, g16.float(), arg, x32)
+                return x32.to(T)
+            a, bb = timeit_pair(native, twin), timeit_pair(native, twin)
+            line("pool_max_grad", {"level": tag, "scenes": scenes, "rows": rows, "ns": ns}, (a[0], bb[0]), (a[1], bb[1]),
+                 timeit_pair(native, upcast), rows * (ns * 2 + 2 + 4), rows * (ns * 4 + 4 + 4))
+            del x32, x16, o16, o32, g16, g32
+        # ---- three_interpolate: (b, c, m, n) of the four FP levels
+        for tag, (b, c, m, n) in (("fp1", (scenes, 256, 4096, 16384)), ("fp2", (scenes, 512, 1024, 4096)), ("fp3", (scenes, 512, 256, 1024)),
+                                  ("fp4", (scenes, 1024, 64, 256))):
+            p32 = torch.randn((b, c, m), generator=g, device=dev)
+            p16 = p32.to(T)
+            idx = torch.randint(0, m, (b, n, 3), generator=g, device=dev, dtype=i32)
+            wt = torch.rand((b, n, 3), generator=g, device=dev)
+            o16, o32 = torch.empty((b, c, n), dtype=T, device=dev), torch.empty((b, c, n), dtype=f32, device=dev)
+            native = lambda: p2.three_interpolate_h_wrapper(b, c, m, n, p16, idx, wt, o16)      # noqa: E731
+            twin = lambda: p2.three_interpolate_wrapper(b, c, m, n, p32, idx, wt, o32)          # noqa: E731
+
+            def upcast():
+                p2.three_interpolate_wrapper(b, c, m, n, p16.float(), idx, wt, o32)
+                return o32.to(T)
+            a, bb = timeit_pair(native, twin), timeit_pair(native, twin)
+            per = lambda e: b * (c * m * e + n * 24 + c * n * e)                                   # noqa: E731
+            line("three_interpolate", {"level": tag, "scenes": scenes, "b": b, "c": c, "m": m, "n": n}, (a[0], bb[0]), (a[1], bb[1]),
+                 timeit_pair(native, upcast), per(2), per(4))
+            del p32, p16, o16, o32
+
+
 def kitti_eval_rows(args):
     """the AP evaluator (epnet_amd.kitti_eval) on a seeded synthetic set: median wall time of the whole get_official_eval_result
     (class Car) and of its phases, and the same set -- cut down to --kitti-eval-host-frames -- through the numpy restatement of
@@ -681,6 +773,8 @@ def main():
     ap.add_argument("--optim-side", default="both", choices=["both", "fused", "fused_views", "composed"],
                     help="with --optim-only: run one side alone (what a kernel trace of launches per step needs); fused_views: the fused "
                          "side with every gradient a view at an odd offset of one bucket")
+    ap.add_argument("--rows16-only", action="store_true",
+                    help="only the native 16-bit SA / FP kernels against their float32 twins and the upcast composition (bf16)")
     ap.add_argument("--kitti-eval-only", action="store_true",
                     help="only the AP evaluator: get_official_eval_result and its phases on a synthetic set at KITTI-val scale")
     ap.add_argument("--kitti-eval-frames", type=int, default=3769, help="frames of the synthetic set (KITTI val: 3769)")
@@ -809,6 +903,8 @@ def main():
         return scan_rows(args, report, timeit_pair)
     if args.handover_only:
         return handover_rows(args, report, timeit_pair)
+    if args.rows16_only:
+        return rows16_rows(args, timeit_pair)
     # ---- NMS at the proposal-layer sizes (RPN.NMS_TYPE normal, N <= 6300 / 2700, thresh 0.85) and eval rotated NMS
     for n, rot, thr in ((6300, False, 0.85), (2700, False, 0.85), (6300, True, 0.8), (512, True, 0.1), (100, True, 0.1)):
         boxes, scores = synth.proposal_boxes(n, seed=n, num_objects=40, jitter=1.5)

@@ -4,6 +4,7 @@
 
     python bench_step.py --image --rpn-only [--batch 2]       # config 3: two-stream RPN (point + image stream, LI-Fusion) fwd+bwd
     python bench_step.py --image [--gpus N]                   # config 4: the whole rcnn_online step, 62.7 MB of gradients
+    python bench_step.py --image [--rpn-only] --amp bf16      # either under torch.autocast("cuda", torch.bfloat16)
     python bench_step.py                                      # the point stream alone (round-1 figure)
     python bench_step.py --infer [--two-stage]                # inference latency: the RPN stage [and the whole detector]
     python bench_step.py --infer --two-stage --proposals fused   # the same with the one-call RPN hand-over (epnet_rpn_handover)
@@ -306,6 +307,10 @@ def main():
                     help="where the step starts: from the (B,N,3) point arrays a loader would hand over (default), or, with --rpn-only, "
                          "from raw scans (synth.lidar_scan, 122 880 points each) through scan_layer.prepare_scans and "
                          "rpn_target_layer.augment_and_label on the device, fresh draws every step, no host synchronisation")
+    ap.add_argument("--amp", default="off", choices=["off", "bf16"],
+                    help="bf16: forward under torch.autocast('cuda', torch.bfloat16) -- dense layers and this package's SA / FP operators on "
+                         "bfloat16 rows, parameters and their gradients float32 (float16 is not offered: training in it needs loss "
+                         "scaling, which FusedAdamOneCycle does not do)")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without a torch.distributed.run environment the ranks are started as child processes")
     ap.add_argument("--launch-check", action="store_true", help="rehearse the N-rank launch only (see bench.py)")
@@ -412,7 +417,8 @@ def main():
         step_xyz, step_gts = step_inputs()
         if raw is not None and timed:
             mark("inputs")
-        loss, out = run_step(model, layers, step_xyz, step_gts, mark if timed else None, image, xy, args.rpn_only)
+        with torch.autocast("cuda", torch.bfloat16, enabled=args.amp == "bf16"):
+            loss, out = run_step(model, layers, step_xyz, step_gts, mark if timed else None, image, xy, args.rpn_only)
         if timed:                                              # the line carries the terms of the last TIMED step
             last_out.update({k: v for k, v in out.items() if k in ("rpn_loss", "rcnn_loss")})
         loss.backward()
@@ -523,7 +529,7 @@ def main():
                           "devices": [r_["device"] for r_ in per_rank], "rehearsal": bool(args.rehearsal),
                           "per_rank_ms_per_step": {"min": min(r_["ms_per_step"] for r_ in per_rank),
                                                    "max": max(r_["ms_per_step"] for r_ in per_rank)},
-                          "loss": last, "data": "synthetic", "dtype": "f32", **({} if raw is None else {"inputs": "raw"}),
+                          "loss": last, "data": "synthetic", "dtype": "f32" if args.amp == "off" else "bf16 autocast (parameters f32)", **({} if raw is None else {"inputs": "raw"}),
                           **({} if args.optimizer == "sgd" else {"optimizer": args.optimizer}),
                           **({} if args.optimizer != "fused" else {"optimizer_stats": dict(zip(optim.optim_cuda.STATS_NAMES, opt.stats.tolist()))}),
                           **({} if args.loss == "placeholder" else {"loss_mode": args.loss, "loss_terms": {

@@ -66,6 +66,10 @@ SIGNATURES = {
     "epnet_group_linear_grad_w_det": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "epnet_pool_max": (_i, [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp]),
     "epnet_pool_max_grad": (_i, [ctypes.c_longlong, _i, _vp, _vp, _vp, _vp]),
+    "epnet_group_linear_h": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "epnet_pool_max_h": (_i, [ctypes.c_longlong, _i, _vp, _vp, _vp, _i, _vp]),
+    "epnet_pool_max_grad_h": (_i, [ctypes.c_longlong, _i, _vp, _vp, _vp, _i, _vp]),
+    "epnet_three_interpolate_h": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "epnet_scene_index_bytes": (_sz, [_i, _i]),
     "epnet_scene_index_build": (_i, [_i, _i, _vp, _vp, _sz, _vp]),
     "epnet_scene_index_build_gathered": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

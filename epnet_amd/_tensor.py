@@ -21,6 +21,42 @@ def dev_ptr(t, name, dtype):
     return t.data_ptr()
 
 
+# the 16-bit feature types of torch.autocast and their codes in include/epnet_ops.h (EPNET_F16, EPNET_BF16)
+ROWS16 = {torch.float16: 1, torch.bfloat16: 2}
+
+
+def is_rows16(t):
+    return isinstance(t, torch.Tensor) and t.dtype in ROWS16
+
+
+def dev_ptr16(t, name, dtype):
+    """dev_ptr for the 16-bit feature rows of the *_h entry points: `dtype` is one of ROWS16 (float64 and every other type
+    raise exactly as dev_ptr does)"""
+    if dtype not in ROWS16:
+        _bad(name, "must have dtype torch.float32, torch.float16 or torch.bfloat16, got %s" % dtype)
+    return dev_ptr(t, name, dtype)
+
+
+def as_f32(t):
+    """the one upcast at a boundary of the 16-bit path (DESIGN 4.10): a float16 / bfloat16 tensor becomes float32 (exact;
+    autograd casts the gradient back to the tensor's own type), anything else -- float32, integers, None -- passes unchanged,
+    so a float32 caller runs exactly what it ran before"""
+    return t.float() if is_rows16(t) else t
+
+
+def f32_region(fn):
+    """decorator of a head-side entry point (losses, proposal / target / detection layers): its body is box geometry on the
+    float32 tensors `as_f32` made, so an enclosing torch.autocast must not turn its matmuls into 16-bit ones. Outside autocast
+    this changes nothing."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(*args, **kwargs):
+        with torch.autocast("cuda", enabled=False):
+            return fn(*args, **kwargs)
+    return wrapped
+
+
 def host_ptr(t, name, dtype):
     if not isinstance(t, torch.Tensor):
         _bad(name, "must be a torch.Tensor")

@@ -20,6 +20,7 @@ import torch.nn as nn
 from . import iou3d_cuda
 from . import roipool3d_utils
 from .bbox_transform import decode_bbox_target
+from ._tensor import as_f32, f32_region
 
 
 def default_cfg():
@@ -42,12 +43,14 @@ def _ambient_cfg():
     return ref.cfg if ref is not None and hasattr(ref, "cfg") else default_cfg()
 
 
+@f32_region
 def pool_rois(rpn_xyz, rpn_features, roi_boxes3d, seg_mask, pts_depth=None, rpn_intensity=None, cfg=None):
     """lib/net/rcnn_net.py:138-164: rpn_xyz (B,N,3), rpn_features (B,N,C), roi_boxes3d (B,M,7), seg_mask (B,N), pts_depth
     (B,N) with RCNN.USE_DEPTH, rpn_intensity (B,N) with RCNN.USE_INTENSITY -> pts_input (B*M, S, 3 + extra + C) in each ROI's
     own frame and pooled_empty_flag (B,M) int32. The extra-input columns come in the reference's order: intensity, mask,
     depth."""
     cfg = cfg if cfg is not None else _ambient_cfg()
+    rpn_features = as_f32(rpn_features)   # bf16 / fp16 backbone output: upcast once here
     if cfg.RCNN.USE_INTENSITY:
         extra = [rpn_intensity.unsqueeze(dim=2), seg_mask.unsqueeze(dim=2)]              # :140-142
     else:
@@ -70,12 +73,14 @@ class DetectionLayer(nn.Module):
         self.fused_decode = bool(fused_decode)
         self.register_buffer("MEAN_SIZE", torch.from_numpy(np.asarray(self.cfg.CLS_MEAN_SIZE[0], dtype=np.float32)), persistent=False)
 
+    @f32_region
     def forward(self, rois, rcnn_cls, rcnn_reg, rcnn_iou_branch=None):
         """rois (B,M,7), rcnn_cls (B*M,1), rcnn_reg (B*M,C), rcnn_iou_branch (B*M,1) with USE_IOU_BRANCH -> pred_boxes3d
         (B,M,7), raw_scores (B,M), norm_scores (B,M), det_boxes3d (B,M,7), det_scores (B,M), det_count (B) int32: the
         detections of scene k are det_boxes3d[k, :det_count[k]], highest raw score first, zero rows behind"""
         rcnn = self.cfg.RCNN
         batch_size = rois.shape[0]
+        rcnn_cls, rcnn_reg, rcnn_iou_branch = as_f32(rcnn_cls), as_f32(rcnn_reg), as_f32(rcnn_iou_branch)   # bf16 / fp16 heads
         rcnn_cls = rcnn_cls.view(batch_size, -1, rcnn_cls.shape[1])                      # :555
         rcnn_reg = rcnn_reg.view(batch_size, -1, rcnn_reg.shape[1])                      # :556
         if rcnn_iou_branch is not None:                                                  # :558-561

@@ -24,6 +24,7 @@ from torch.autograd.function import once_differentiable
 
 from . import loss_cuda
 from . import pointnet2_utils
+from ._tensor import as_f32, f32_region
 
 # the order of `terms` (EPNET_BOX_LOSS_TERMS, include/epnet_ops.h)
 TERM_NAMES = ["total", "loss", "loss_cls", "loss_cls_pos", "loss_cls_neg", "loss_reg", "loss_loc", "loss_angle", "loss_size", "loss_iou",
@@ -159,10 +160,12 @@ def _run(stage_cfg, cfg, names, cls_logit, pred_reg, reg_label, cls_label, reg_m
     return LossReturn(total, terms, names)
 
 
+@f32_region
 def rpn_loss(rpn_cls, rpn_reg, rpn_cls_label, rpn_reg_label, cfg=None):
     """get_rpn_loss, train_functions.py:92-163, times TRAIN.RPN_TRAIN_WEIGHT (:60): rpn_cls (B,N,1), rpn_reg (B,N,C),
     rpn_cls_label (B,N) in {-1, 0, 1}, rpn_reg_label (B,N,7) -> LossReturn(loss, terms, RPN_TERM_NAMES)"""
     cfg = cfg if cfg is not None else _ambient_cfg()
+    rpn_cls, rpn_reg = as_f32(rpn_cls), as_f32(rpn_reg)   # bf16 / fp16 heads: one upcast; autograd casts the gradients back
     if not cfg.RPN.LOC_XZ_FINE:
         raise NotImplementedError("RPN.LOC_XZ_FINE = False: the reference's IoU term reads x_res_l, which that configuration "
                                   "never defines (loss_utils.py:235)")
@@ -170,6 +173,7 @@ def rpn_loss(rpn_cls, rpn_reg, rpn_cls_label, rpn_reg_label, cfg=None):
                 cfg.RPN.LOSS_WEIGHT[0], cfg.RPN.LOSS_WEIGHT[1], cfg.TRAIN.RPN_TRAIN_WEIGHT, cfg.RPN.FG_WEIGHT)
 
 
+@f32_region
 def rcnn_loss(ret_dict, cfg=None):
     """get_rcnn_loss, train_functions.py:165-284, times TRAIN.RCNN_TRAIN_WEIGHT (:74): reads rcnn_cls (R,1), rcnn_reg (R,C),
     cls_label (R), reg_valid_mask (R), gt_of_rois (R,7) and, with USE_IOU_BRANCH, rcnn_iou_branch (R,1) -- the keys
@@ -180,6 +184,6 @@ def rcnn_loss(ret_dict, cfg=None):
                                   "never defines (loss_utils.py:236)")
     if cfg.RCNN.SIZE_RES_ON_ROI:
         raise NotImplementedError("RCNN.SIZE_RES_ON_ROI (per-ROI anchors; the anchor is the 3-vector CLS_MEAN_SIZE here)")
-    branch = ret_dict["rcnn_iou_branch"] if cfg.USE_IOU_BRANCH else None
-    return _run(cfg.RCNN, cfg, RCNN_TERM_NAMES, ret_dict["rcnn_cls"], ret_dict["rcnn_reg"], ret_dict["gt_of_rois"], ret_dict["cls_label"],
+    branch = as_f32(ret_dict["rcnn_iou_branch"]) if cfg.USE_IOU_BRANCH else None   # bf16 / fp16 heads, as rpn_loss
+    return _run(cfg.RCNN, cfg, RCNN_TERM_NAMES, as_f32(ret_dict["rcnn_cls"]), as_f32(ret_dict["rcnn_reg"]), ret_dict["gt_of_rois"], ret_dict["cls_label"],
                 ret_dict["reg_valid_mask"], branch, True, 1.0, 1.0, cfg.TRAIN.RCNN_TRAIN_WEIGHT, 1.0)

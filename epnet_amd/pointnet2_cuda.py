@@ -9,7 +9,7 @@ ABI in libepnet_hip.so. Failures raise RuntimeError; the reference prints and ex
 import torch
 
 from . import _lib
-from ._tensor import dev_ptr, need, on_device_of, writes
+from ._tensor import ROWS16, dev_ptr, dev_ptr16, need, on_device_of, writes
 
 _F, _I = torch.float32, torch.int32
 
@@ -475,6 +475,61 @@ def group_linear_grad_w_wrapper(b, c, n, npoints, nsample, grad_out, xyz, new_xy
         return 1
     with on_device_of(grad_out) as s:
         _lib.check(_lib.lib().epnet_group_linear_grad_w(b, c, n, npoints, nsample, pg, px, pn, pi, pw, s), "group_linear_grad_w")
+    return 1
+
+
+# ---- 16-bit feature rows (torch.autocast): the native *_h entry points of csrc/rows16.hip ---------------------------------------
+# Feature tensors are float16 or bfloat16 (one type per call); coordinates, weights, bias and indices stay float32 / int32.
+# Result = the float32 stand-in above on the upcast rows, rounded once to the 16-bit type (include/epnet_ops.h).
+
+
+@writes("out")
+def group_linear_h_wrapper(b, c, n, npoints, nsample, xyz, new_xyz, z, idx, w_xyz, bias, out):
+    """group_linear_wrapper with z and out float16 / bfloat16"""
+    px, pn, pz = dev_ptr(xyz, "xyz", _F), dev_ptr(new_xyz, "new_xyz", _F), dev_ptr16(z, "z", z.dtype)
+    pi, pw, po = dev_ptr(idx, "idx", _I), dev_ptr(w_xyz, "w_xyz", _F), dev_ptr(out, "out", z.dtype)
+    pb = dev_ptr(bias, "bias", _F) if bias is not None else None
+    need(xyz, b * n * 3, "xyz"); need(new_xyz, b * npoints * 3, "new_xyz"); need(z, b * c * n, "z")
+    need(idx, b * npoints * nsample, "idx"); need(w_xyz, c * 3, "w_xyz"); need(out, b * c * npoints * nsample, "out")
+    if bias is not None:
+        need(bias, c, "bias")
+    with on_device_of(z) as s:
+        _lib.check(_lib.lib().epnet_group_linear_h(b, c, n, npoints, nsample, px, pn, pz, pi, pw, pb, po, ROWS16[z.dtype], s),
+                   "group_linear")
+    return 1
+
+
+@writes("out", "arg")
+def pool_max_h_wrapper(rows, nsample, x, out, arg):
+    """pool_max_wrapper with x and out float16 / bfloat16 (the winner's own 16 bits)"""
+    px, po = dev_ptr16(x, "x", x.dtype), dev_ptr(out, "out", x.dtype)
+    pa = dev_ptr(arg, "arg", _I) if arg is not None else None
+    need(x, rows * nsample, "x"); need(out, rows, "out")
+    if arg is not None:
+        need(arg, rows, "arg")
+    with on_device_of(x) as s:
+        _lib.check(_lib.lib().epnet_pool_max_h(rows, nsample, px, po, pa, ROWS16[x.dtype], s), "pool_max")
+    return 1
+
+
+@writes("grad_x")
+def pool_max_grad_h_wrapper(rows, nsample, grad_out, arg, grad_x):
+    """pool_max_grad_wrapper with grad_out and grad_x float16 / bfloat16"""
+    pg, pa, px = dev_ptr16(grad_out, "grad_out", grad_out.dtype), dev_ptr(arg, "arg", _I), dev_ptr(grad_x, "grad_x", grad_out.dtype)
+    need(grad_out, rows, "grad_out"); need(arg, rows, "arg"); need(grad_x, rows * nsample, "grad_x")
+    with on_device_of(grad_out) as s:
+        _lib.check(_lib.lib().epnet_pool_max_grad_h(rows, nsample, pg, pa, px, ROWS16[grad_out.dtype], s), "pool_max_grad")
+    return 1
+
+
+@writes("out")
+def three_interpolate_h_wrapper(b, c, m, n, points, idx, weight, out):
+    """three_interpolate_wrapper with points and out float16 / bfloat16"""
+    pp, pi = dev_ptr16(points, "points", points.dtype), dev_ptr(idx, "idx", _I)
+    pw, po = dev_ptr(weight, "weight", _F), dev_ptr(out, "out", points.dtype)
+    need(points, b * c * m, "points"); need(idx, b * n * 3, "idx"); need(weight, b * n * 3, "weight"); need(out, b * c * n, "out")
+    with on_device_of(points) as s:
+        _lib.check(_lib.lib().epnet_three_interpolate_h(b, c, m, n, pp, pi, pw, po, ROWS16[points.dtype], s), "three_interpolate")
     return 1
 
 

@@ -19,12 +19,17 @@ from . import pointnet2_utils
 from . import pytorch_utils as pt_utils
 
 
+# what the fused path takes: float32, and under torch.autocast the two 16-bit types (pointnet2_utils: native group_linear and
+# pool_max kernels, so a level runs matmul -> group_linear -> rest of the MLP -> pool_max entirely in the autocast type)
+_FEATURE_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
 def _foldable(grouper, mlp, features) -> bool:
     """can the first layer of `mlp` be folded into the grouping? A ball-query grouper that prepends xyz, features present,
     and a first unit that starts with a plain 1x1 convolution over [xyz(3) ; features(C)]"""
     if not isinstance(grouper, pointnet2_utils.QueryAndGroup) or not grouper.use_xyz or features is None:
         return False
-    if features.dtype != torch.float32 or len(mlp) == 0:
+    if features.dtype not in _FEATURE_DTYPES or len(mlp) == 0:
         return False
     first = mlp[0]
     children = list(first.children())
@@ -49,7 +54,7 @@ class _PointnetSAModuleBase(nn.Module):
     def _pool(self, x: torch.Tensor) -> torch.Tensor:
         window = [1, x.size(3)]
         if self.pool_method == 'max_pool':
-            if x.is_cuda and x.dtype == torch.float32 and x.size(3) > 0:
+            if x.is_cuda and x.dtype in _FEATURE_DTYPES and x.size(3) > 0:
                 return pointnet2_utils.pool_max(x)  # same values as the stock op below, rows read with coalesced loads
             return F.max_pool2d(x, kernel_size=window)
         if self.pool_method == 'avg_pool':

@@ -7,6 +7,16 @@ same call signatures, dtypes and output shapes. Differences from the reference a
 plumbing: outputs are allocated on the INPUT's device (the reference uses
 ``torch.cuda.FloatTensor(...)``, i.e. whatever device is current), and errors raise instead of
 killing the process.
+
+16-bit features (``torch.autocast``). A float16 / bfloat16 FEATURE tensor is accepted by every op here; the
+result is the value the float32 op gives on the upcast features, rounded once to that type (coordinates, weights, bias and
+indices stay float32 / int32; float64 still raises). NATIVE 16-bit kernels: ``group_linear``, ``pool_max`` forward and
+backward, ``three_interpolate`` forward. UPCAST route (the float32 kernel, then one ``.to(T)``): ``gather_operation``,
+``grouping_operation``, the gradients of ``group_linear`` (``grad_z``; ``grad_w`` / ``grad_b`` come back float32, the
+parameters' type) and of ``three_interpolate``, ``group_concat`` / ``group_concat_multi`` / ``QueryAndGroup`` (float32 out with
+``use_xyz=True`` -- the stock promotion of ``cat(fp32 xyz, T features)`` -- and ``T`` with ``use_xyz=False``) and every
+deterministic (``_det``) twin. float16 is for inference and single ops: training in it needs loss scaling, which
+``FusedAdamOneCycle`` does not do; train under ``torch.autocast("cuda", torch.bfloat16)``.
 """
 import os
 import threading
@@ -17,6 +27,12 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import pointnet2_cuda as _ext
+from ._tensor import is_rows16 as _is16
+
+
+def _up(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """the upcast route of the 16-bit path (module docstring): float16 / bfloat16 -> float32 (exact), anything else unchanged"""
+    return t.float() if _is16(t) else t
 
 
 def _new(like: torch.Tensor, shape, dtype=torch.float32, zero: bool = False) -> torch.Tensor:
@@ -190,17 +206,17 @@ class GatherOperation(Function):
         batch, npoint = idx.shape
         channels, n = features.shape[1], features.shape[2]
         out = _new(features, (batch, channels, npoint))
-        _ext.gather_points_wrapper(batch, channels, n, npoint, features, idx, out)
+        _ext.gather_points_wrapper(batch, channels, n, npoint, _up(features), idx, out)
         ctx.for_backwards = (idx, channels, n)
-        return out
+        return out.to(features.dtype) if _is16(features) else out
 
     @staticmethod
     def backward(ctx, grad_out):
         idx, channels, n = ctx.for_backwards
         batch, npoint = idx.shape
         grad_features = _new(grad_out, (batch, channels, n), zero=True)
-        _ext.gather_points_grad_wrapper(batch, channels, n, npoint, grad_out.detach().contiguous(), idx, grad_features)
-        return grad_features, None
+        _ext.gather_points_grad_wrapper(batch, channels, n, npoint, _up(grad_out.detach()).contiguous(), idx, grad_features)
+        return (grad_features.to(grad_out.dtype) if _is16(grad_out) else grad_features), None
 
 
 gather_operation = GatherOperation.apply
@@ -243,6 +259,10 @@ class ThreeInterpolate(Function):
         batch, channels, m = features.shape
         n = idx.shape[1]
         ctx.three_interpolate_for_backward = (idx, weight, m)
+        if _is16(features):   # native 16-bit kernel
+            out = _new(features, (batch, channels, n), features.dtype)
+            _ext.three_interpolate_h_wrapper(batch, channels, m, n, features, idx, weight, out)
+            return out
         out = _new(features, (batch, channels, n))
         _ext.three_interpolate_wrapper(batch, channels, m, n, features, idx, weight, out)
         return out
@@ -252,9 +272,9 @@ class ThreeInterpolate(Function):
         idx, weight, m = ctx.three_interpolate_for_backward
         batch, channels, n = grad_out.shape
         grad_features = _new(grad_out, (batch, channels, m), zero=True)
-        _ext.three_interpolate_grad_wrapper(batch, channels, n, m, grad_out.detach().contiguous(), idx, weight,
+        _ext.three_interpolate_grad_wrapper(batch, channels, n, m, _up(grad_out.detach()).contiguous(), idx, weight,
                                             grad_features)
-        return grad_features, None, None
+        return (grad_features.to(grad_out.dtype) if _is16(grad_out) else grad_features), None, None
 
 
 three_interpolate = ThreeInterpolate.apply
@@ -270,18 +290,18 @@ class GroupingOperation(Function):
         batch, npoint, nsample = idx.shape
         channels, n = features.shape[1], features.shape[2]
         out = _new(features, (batch, channels, npoint, nsample))
-        _ext.group_points_wrapper(batch, channels, n, npoint, nsample, features, idx, out)
+        _ext.group_points_wrapper(batch, channels, n, npoint, nsample, _up(features), idx, out)
         ctx.for_backwards = (idx, n)
-        return out
+        return out.to(features.dtype) if _is16(features) else out
 
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
         idx, n = ctx.for_backwards
         batch, channels, npoint, nsample = grad_out.shape
         grad_features = _new(grad_out, (batch, channels, n), zero=True)
-        _ext.group_points_grad_wrapper(batch, channels, n, npoint, nsample, grad_out.detach().contiguous(), idx,
+        _ext.group_points_grad_wrapper(batch, channels, n, npoint, nsample, _up(grad_out.detach()).contiguous(), idx,
                                        grad_features)
-        return grad_features, None
+        return (grad_features.to(grad_out.dtype) if _is16(grad_out) else grad_features), None
 
 
 grouping_operation = GroupingOperation.apply
@@ -339,9 +359,11 @@ class _GroupConcat(Function):
         n = xyz.shape[1]
         channels = 0 if features is None else features.shape[1]
         out = _new(xyz, (batch, (3 if use_xyz else 0) + channels, npoint, nsample))
-        _ext.group_concat_wrapper(batch, channels, n, npoint, nsample, xyz, new_xyz, features, idx, out, use_xyz)
+        _ext.group_concat_wrapper(batch, channels, n, npoint, nsample, xyz, new_xyz, _up(features), idx, out, use_xyz)
         ctx.for_backwards = (idx, channels, n, use_xyz)
-        return out
+        ctx.feature_dtype = features.dtype if _is16(features) else None
+        # 16-bit features: float32 beside the float32 coordinates (torch.cat's promotion), their own type alone
+        return out.to(features.dtype) if _is16(features) and not use_xyz else out
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -350,8 +372,10 @@ class _GroupConcat(Function):
             return None, None, None, None, None
         batch, _, npoint, nsample = grad_out.shape
         grad_features = _new(grad_out, (batch, channels, n), zero=True)
-        _ext.group_concat_grad_wrapper(batch, channels, n, npoint, nsample, grad_out.detach().contiguous(), idx,
+        _ext.group_concat_grad_wrapper(batch, channels, n, npoint, nsample, _up(grad_out.detach()).contiguous(), idx,
                                        grad_features, use_xyz)
+        if ctx.feature_dtype is not None:
+            grad_features = grad_features.to(ctx.feature_dtype)
         return None, None, grad_features, None, None
 
 
@@ -366,8 +390,11 @@ class _GroupConcatMulti(Function):
         channels = 0 if features is None else features.shape[1]
         nsamples = [int(i.shape[2]) for i in idxs]
         outs = [_new(xyz, (batch, (3 if use_xyz else 0) + channels, npoint, ns)) for ns in nsamples]
-        _ext.group_concat_multi_wrapper(batch, channels, n, npoint, nsamples, xyz, new_xyz, features, list(idxs), outs, use_xyz)
+        _ext.group_concat_multi_wrapper(batch, channels, n, npoint, nsamples, xyz, new_xyz, _up(features), list(idxs), outs, use_xyz)
         ctx.for_backwards = (idxs, channels, n, use_xyz)
+        ctx.feature_dtype = features.dtype if _is16(features) else None
+        if _is16(features) and not use_xyz:   # as _GroupConcat
+            outs = [o.to(features.dtype) for o in outs]
         return tuple(outs)
 
     @staticmethod
@@ -380,7 +407,9 @@ class _GroupConcatMulti(Function):
         grad_features = _new(grad_outs[0], (batch, channels, n), zero=True)
         for idx, g in zip(idxs, grad_outs):   # the gradient op accumulates into its output, like the reference's atomicAdd
             npoint, nsample = idx.shape[1], idx.shape[2]
-            _ext.group_concat_grad_wrapper(batch, channels, n, npoint, nsample, g.detach().contiguous(), idx, grad_features, use_xyz)
+            _ext.group_concat_grad_wrapper(batch, channels, n, npoint, nsample, _up(g.detach()).contiguous(), idx, grad_features, use_xyz)
+        if ctx.feature_dtype is not None:
+            grad_features = grad_features.to(ctx.feature_dtype)
         return (None, None, grad_features, None) + (None,) * len(idxs)
 
 
@@ -401,8 +430,12 @@ class _GroupLinear(Function):
     def forward(ctx, xyz, new_xyz, z, idx, w_xyz, bias):
         b, c, n = z.shape
         npoint, nsample = idx.shape[1], idx.shape[2]
-        out = _new(z, (b, c, npoint, nsample))
-        _ext.group_linear_wrapper(b, c, n, npoint, nsample, xyz, new_xyz, z, idx, w_xyz, bias, out)
+        if _is16(z):   # native 16-bit kernel
+            out = _new(z, (b, c, npoint, nsample), z.dtype)
+            _ext.group_linear_h_wrapper(b, c, n, npoint, nsample, xyz, new_xyz, z, idx, w_xyz, bias, out)
+        else:
+            out = _new(z, (b, c, npoint, nsample))
+            _ext.group_linear_wrapper(b, c, n, npoint, nsample, xyz, new_xyz, z, idx, w_xyz, bias, out)
         ctx.save_for_backward(xyz, new_xyz, idx)
         ctx.dims = (b, c, n, npoint, nsample, bias is not None)
         return out
@@ -411,11 +444,13 @@ class _GroupLinear(Function):
     def backward(ctx, grad_out):
         xyz, new_xyz, idx = ctx.saved_tensors
         b, c, n, npoint, nsample, has_bias = ctx.dims
-        g = grad_out.detach().contiguous()
+        g = _up(grad_out.detach()).contiguous()   # 16-bit: the float32 gradient ops on the upcast grad_out
         grad_z = grad_w = grad_b = None
         if ctx.needs_input_grad[2]:      # scatter-add over the neighbour lists, as for any grouped tensor
             grad_z = _new(g, (b, c, n), zero=True)
             _ext.group_points_grad_wrapper(b, c, n, npoint, nsample, g, idx, grad_z)
+            if _is16(grad_out):
+                grad_z = grad_z.to(grad_out.dtype)   # rounded once; grad_w and grad_b stay float32, the parameters' type
         if ctx.needs_input_grad[4]:      # d out / d w_xyz = the centred neighbour coordinates, rebuilt inside the reduction
             grad_w = _new(g, (c, 3), zero=True)
             _ext.group_linear_grad_w_wrapper(b, c, n, npoint, nsample, g, xyz, new_xyz, idx, grad_w)
@@ -425,7 +460,8 @@ class _GroupLinear(Function):
 
 
 def group_linear(xyz, new_xyz, z, idx, w_xyz, bias=None):
-    """(B,N,3), (B,M,3), z (B,C,N), idx (B,M,ns) int32, w_xyz (C,3), bias (C) -> (B,C,M,ns)"""
+    """(B,N,3), (B,M,3), z (B,C,N), idx (B,M,ns) int32, w_xyz (C,3), bias (C) -> (B,C,M,ns). z may be float16 / bfloat16
+    (native kernel; out has z's type, w_xyz and bias stay float32)"""
     return _GroupLinear.apply(xyz.contiguous(), new_xyz.contiguous(), z.contiguous(), idx, w_xyz.contiguous(),
                               None if bias is None else bias.contiguous())
 
@@ -440,16 +476,24 @@ class _PoolMax(Function):
         x = x.contiguous()
         nsample = x.shape[-1]
         rows = x.numel() // max(nsample, 1)
-        out = _new(x, x.shape[:-1] + (1,))
         need_grad = ctx.needs_input_grad[0]
         arg = _new(x, x.shape[:-1], dtype=torch.int32) if need_grad else None
-        _ext.pool_max_wrapper(rows, nsample, x, out, arg)
+        if _is16(x):   # native 16-bit kernel
+            out = _new(x, x.shape[:-1] + (1,), x.dtype)
+            _ext.pool_max_h_wrapper(rows, nsample, x, out, arg)
+        else:
+            out = _new(x, x.shape[:-1] + (1,))
+            _ext.pool_max_wrapper(rows, nsample, x, out, arg)
         ctx.for_backwards = (arg, tuple(x.shape))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         arg, shape = ctx.for_backwards
+        if _is16(grad_out):   # native 16-bit kernel
+            grad_x = _new(grad_out, shape, grad_out.dtype)
+            _ext.pool_max_grad_h_wrapper(grad_x.numel() // shape[-1], shape[-1], grad_out.detach().contiguous(), arg, grad_x)
+            return grad_x
         grad_x = _new(grad_out, shape)
         _ext.pool_max_grad_wrapper(grad_x.numel() // shape[-1], shape[-1], grad_out.detach().contiguous(), arg, grad_x)
         return grad_x

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import iou3d_cuda
 from .bbox_transform import decode_bbox_target
+from ._tensor import as_f32, f32_region
 
 
 def default_cfg():
@@ -63,9 +64,11 @@ class ProposalLayer(nn.Module):
         proposals[:, 1] += proposals[:, 3] / 2
         return proposals.view(batch_size, -1, 7)
 
+    @f32_region
     def forward(self, rpn_scores, rpn_reg, xyz):
         """rpn_scores (B,N), rpn_reg (B,N,C), xyz (B,N,3) -> ret_bbox3d (B,M,7), ret_scores (B,M), M = RPN_POST_NMS_TOP_N,
         zero rows behind the kept proposals"""
+        rpn_scores, rpn_reg = as_f32(rpn_scores), as_f32(rpn_reg)   # bf16 / fp16 heads: upcast once here
         if self.fused_head:
             from . import handover_cuda, rpn_handover
             args = rpn_handover.handover_args(self.cfg, self.mode)

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import iou3d_cuda, iou3d_utils, kitti_utils, roipool3d_utils
+from ._tensor import as_f32, f32_region
 
 # pos_range, hwl_range, angle_range of random_aug_box3d's 'multiple' method (:263-267; the 4th column, mean_iou, is unused)
 _RANGE_CONFIG = ((0.2, 0.1, np.pi / 12), (0.3, 0.15, np.pi / 12), (0.5, 0.15, np.pi / 9), (0.8, 0.15, np.pi / 6),
@@ -124,12 +125,13 @@ class ProposalTargetLayer(nn.Module):
         self.generator = generator  # device generator for the augmentation draws (None: the default one)
 
     # ------------------------------------------------------------------------------------------------------ forward
+    @f32_region
     def forward(self, input_dict):
         cfg = self.cfg
-        roi_boxes3d, gt_boxes3d = input_dict['roi_boxes3d'], input_dict['gt_boxes3d']
+        roi_boxes3d, gt_boxes3d = as_f32(input_dict['roi_boxes3d']), input_dict['gt_boxes3d']
         batch_rois, batch_gt_of_rois, batch_roi_iou = self.sample_rois_for_rcnn(roi_boxes3d, gt_boxes3d)
 
-        rpn_xyz, rpn_features = input_dict['rpn_xyz'], input_dict['rpn_features']
+        rpn_xyz, rpn_features = input_dict['rpn_xyz'], as_f32(input_dict['rpn_features'])   # bf16 / fp16 backbone output: upcast once here
         if cfg.RCNN.USE_INTENSITY:
             extra = [input_dict['rpn_intensity'].unsqueeze(dim=2), input_dict['seg_mask'].unsqueeze(dim=2)]
         else:

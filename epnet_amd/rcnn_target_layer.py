@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import iou3d_cuda, pointnet2_utils, roipool3d_cuda
 from .proposal_target_layer import _ambient_cfg, default_cfg, draw_aug_tables  # noqa: F401  (default_cfg: part of the surface)
+from ._tensor import as_f32, f32_region
 
 
 def _thresholds(cfg):
@@ -125,16 +126,17 @@ class RCNNTargetLayer(nn.Module):
         self.generator = generator  # device generator for the tables (None: the default one)
         self.label_dtype = label_dtype
 
+    @f32_region
     def forward(self, input_dict, tables=None):
         cfg = self.cfg
-        roi_boxes3d, gt_boxes3d = input_dict['roi_boxes3d'], input_dict['gt_boxes3d']
+        roi_boxes3d, gt_boxes3d = as_f32(input_dict['roi_boxes3d']), input_dict['gt_boxes3d']
         if cfg.RCNN.REG_AUG_METHOD not in ("single", "multiple"):
             raise NotImplementedError("REG_AUG_METHOD %r" % (cfg.RCNN.REG_AUG_METHOD,))
         if tables is None:
             tables = draw_sampling_tables(roi_boxes3d.shape[0], roi_boxes3d.shape[1], cfg, roi_boxes3d.device, self.generator)
         batch_rois, batch_gt_of_rois, batch_roi_iou, scene_info = sample_rois(roi_boxes3d, gt_boxes3d, tables, cfg)
 
-        rpn_xyz, rpn_features = input_dict['rpn_xyz'], input_dict['rpn_features']
+        rpn_xyz, rpn_features = input_dict['rpn_xyz'], as_f32(input_dict['rpn_features'])   # bf16 / fp16 backbone output: upcast once here
         if cfg.RCNN.USE_INTENSITY:
             extra = [input_dict['rpn_intensity'].unsqueeze(dim=2), input_dict['seg_mask'].unsqueeze(dim=2)]
         else:

@@ -16,6 +16,7 @@ import torch
 
 from . import handover_cuda
 from .proposal_layer import _ambient_cfg
+from ._tensor import as_f32, f32_region
 
 RpnHandover = namedtuple("RpnHandover", ["rois", "roi_scores_raw", "seg_mask", "pts_depth", "roi_count", "proposals", "order"])
 
@@ -63,11 +64,13 @@ def handover_args(cfg, mode):
                 pre_nms_top_n=m.RPN_PRE_NMS_TOP_N, post_nms_top_n=m.RPN_POST_NMS_TOP_N, nms_thresh=m.RPN_NMS_THRESH, rotated=rotated)
 
 
+@f32_region
 def rpn_handover(rpn_cls, rpn_reg, backbone_xyz, cfg=None, mode='TRAIN'):
     """rpn_cls (B,N,1) or (B,N), rpn_reg (B,N,C), backbone_xyz (B,N,3) -> RpnHandover(rois (B,M,7), roi_scores_raw (B,M), seg_mask
     (B,N), pts_depth (B,N), roi_count (B) int32, proposals (B,N,7), order (B,N) int64), M = the mode's RPN_POST_NMS_TOP_N: what
     point_rcnn.py:44-52 hands to the RCNN stage, plus the decoded boxes and the order they were proposed in"""
     cfg = cfg if cfg is not None else _ambient_cfg()
+    rpn_cls, rpn_reg = as_f32(rpn_cls), as_f32(rpn_reg)   # bf16 / fp16 heads: upcast once here
     scores = (rpn_cls[:, :, 0] if rpn_cls.dim() == 3 else rpn_cls).float().contiguous()   # :45
     b, n = scores.shape
     if n > MAX_POINTS:

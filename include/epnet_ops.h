@@ -199,6 +199,22 @@ int epnet_pool_max(long long rows, int nsample, const float *x, float *out, int 
 int epnet_pool_max_grad(long long rows, int nsample, const float *grad_out, const int *arg, float *grad_x,
                         epnet_stream_t stream);
 
+/* The same three byte movers on 16-bit feature rows (csrc/rows16.hip; torch.autocast). dtype names the type of the `void *`
+ * rows; coordinates, weights, bias and indices stay fp32 / i32. ONE rule: the result is the value the fp32 entry point above
+ * gives on the rows upcast to fp32, rounded once to the 16-bit type (to nearest, ties to even; denormals kept; overflow gives
+ * +-inf; NaN stays NaN). The max-pool and its gradient move the element's own 16 bits. Same argument validation and error
+ * codes as the fp32 twins; an unknown dtype is EPNET_EINVAL. No alignment is required beyond the element's (the kernels
+ * pick their 16- and 8-byte paths from the pointers). */
+#define EPNET_F16 1
+#define EPNET_BF16 2
+int epnet_group_linear_h(int b, int c, int n, int npoints, int nsample, const float *xyz, const float *new_xyz, const void *z,
+                         const int *idx, const float *w_xyz, const float *bias, void *out, int dtype, epnet_stream_t stream);
+int epnet_pool_max_h(long long rows, int nsample, const void *x, void *out, int *arg, int dtype, epnet_stream_t stream);
+int epnet_pool_max_grad_h(long long rows, int nsample, const void *grad_out, const int *arg, void *grad_x, int dtype,
+                          epnet_stream_t stream);
+int epnet_three_interpolate_h(int b, int c, int m, int n, const void *points, const int *idx, const float *weight, void *out,
+                              int dtype, epnet_stream_t stream);
+
 /* LI-Fusion's point-to-pixel sampler: Feature_Gather of lib/net/pointnet2_msg.py:107-120 =
  * torch grid_sample(feature_map (b,c,h,w), xy (b,1,n,2) in [-1,1]) -> out (b,c,n), bilinear, zero padding, with the
  * torch.gather of xy over the FPS indices (:214-217) folded in: idx (b,n) i32 or NULL picks the rows of xy (b,n_src,2)
