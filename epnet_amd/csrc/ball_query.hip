@@ -124,9 +124,6 @@ __device__ unsigned long long g_bq_stats[16];
 #endif
 #ifdef EPNET_IX_STATS  // diagnostic build only (profiles/micro/ix_stats.py): phase counters of the index build (wave 0)
 __device__ unsigned long long g_ix_stats[8];
-#define EPNET_IX_STAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#else
-#define EPNET_IX_STAMP(var)
 #endif
 
 template <int kIxThreads, int BITS>
@@ -135,228 +132,20 @@ __global__ __launch_bounds__(kIxThreads) void bq_index_kernel(int n, int np, con
                                                               float *__restrict__ qboxes, int n_src = 0,
                                                               const int *__restrict__ src_idx = nullptr,
                                                               float *__restrict__ gathered = nullptr) {
-    constexpr int kCells = 1 << BITS;
-    extern __shared__ int s_hist[];  // cell histogram / running offsets (spatial.h)
+    extern __shared__ int s_hist[];  // cell histogram / running offsets, then the staging rows (spatial.h)
     __shared__ float s_box[6][16];
     __shared__ int s_part[16];
-    const int q = threadIdx.x, lane = q & 63, wave = q >> 6;
     // one workgroup per scene on the sampling chain of a level: beside the wide kernels of the pipelined stack (32 waves of a ball
     // query per CU) its waves would get a ninth of the issue slots -- a 23 us build took 204 us there
     __builtin_amdgcn_s_setprio(3);
-    // src_idx (n <= kIxThreads * 16 only): the scene's points are rows src_idx[0 .. n) of a cloud of n_src points -- the centres a
-    // sampling has just picked -- and are written out in that order as well (gathered): the centre gather of an SA level and the
-    // index build of the next one in one dispatch
-    xyz += (size_t)blockIdx.x * (src_idx ? n_src : n) * 3;
-    if (src_idx) {
-        src_idx += (size_t)blockIdx.x * n;
-        gathered += (size_t)blockIdx.x * n * 3;
-    }
-    sorted += (size_t)blockIdx.x * np;
-    boxes += (size_t)blockIdx.x * (np / 64) * 6;
-    // counting sort by cell, scattering the points (with their original index) straight to global memory.
-    // Up to kIxPerThread points per thread the cloud is read ONCE into registers (bounding box, cell codes and the
-    // scatter all work from there); bigger clouds re-read it per phase.
-    constexpr int per = kCells / kIxThreads;
-    constexpr int per_shift = per == 16 ? 4 : per == 8 ? 3 : per == 4 ? 2 : -1;
-    static_assert(per_shift > 0, "scan layout");
-    constexpr int kIxPerThread = 16;
-    const bool in_regs = n <= kIxThreads * kIxPerThread;  // block-uniform
-    float px[kIxPerThread], py[kIxPerThread], pz[kIxPerThread];
-    float lo[3], ext[3];
-    EPNET_IX_STAMP(t_0);
-    if (in_regs) {
-        float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-        // all of a thread's points are requested before the first one is used, and nothing below branches on `k < n`: with the
-        // box update under an `if` every iteration was a basic block of its own and its load was waited for before the next
-        // was issued -- 16 serial trips to HBM at the head of the sampling chain of every level
-        int row[kIxPerThread];
-#pragma unroll
-        for (int i = 0; i < kIxPerThread; ++i) {
-            const int k = q + i * kIxThreads;
-            const int kk = k < n ? k : 0;
-            row[i] = src_idx ? src_idx[kk] : kk;
-        }
-#pragma unroll
-        for (int i = 0; i < kIxPerThread; ++i) {
-            px[i] = xyz[row[i] * 3 + 0];
-            py[i] = xyz[row[i] * 3 + 1];
-            pz[i] = xyz[row[i] * 3 + 2];
-        }
-        if (src_idx) {
-#pragma unroll
-            for (int i = 0; i < kIxPerThread; ++i) {
-                const int k = q + i * kIxThreads;
-                if (k < n) {
-                    gathered[k * 3 + 0] = px[i];
-                    gathered[k * 3 + 1] = py[i];
-                    gathered[k * 3 + 2] = pz[i];
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < kIxPerThread; ++i) {
-            const bool ok = q + i * kIxThreads < n;
-            mn[0] = fminf(mn[0], ok ? px[i] : 3.4e38f); mx[0] = fmaxf(mx[0], ok ? px[i] : -3.4e38f);
-            mn[1] = fminf(mn[1], ok ? py[i] : 3.4e38f); mx[1] = fmaxf(mx[1], ok ? py[i] : -3.4e38f);
-            mn[2] = fminf(mn[2], ok ? pz[i] : 3.4e38f); mx[2] = fmaxf(mx[2], ok ? pz[i] : -3.4e38f);
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float l = wave_minf_all(mn[a]), h = wave_maxf_all(mx[a]);
-            if (lane == 0) {
-                s_box[a][wave] = l;
-                s_box[3 + a][wave] = h;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            float l = s_box[a][0], h = s_box[3 + a][0];
-            for (int w = 1; w < kIxThreads / 64; ++w) {
-                l = fminf(l, s_box[a][w]);
-                h = fmaxf(h, s_box[3 + a][w]);
-            }
-            lo[a] = l;
-            ext[a] = h - l;
-        }
-    } else {
-        block_bbox3(xyz, n, s_box, lo, ext);
-    }
-    const CellGrid g = make_cell_grid(lo, ext, BITS);
-    EPNET_IX_STAMP(t_1);
-    for (int i = q; i < kCells + kCells / per + 64; i += kIxThreads) s_hist[i] = 0;
-    __syncthreads();
-    EPNET_IX_STAMP(t_2);
-    // in_regs: the histogram pass keeps what its atomics return -- a point's rank inside its cell -- so the scatter below needs
-    // no second round of atomics on the same (hot: a cell next to the sensor holds hundreds of points) words: 46 % of the kernel
-    int code[kIxPerThread], rank[kIxPerThread];
-    if (in_regs) {
-#pragma unroll
-        for (int i = 0; i < kIxPerThread; ++i) code[i] = hist_at((int)cell_code(g, px[i], py[i], pz[i]), per_shift);
-#pragma unroll
-        for (int i = 0; i < kIxPerThread; ++i)   // (a slot beyond n counts on one of the 64 spare words behind the histogram)
-            rank[i] = atomicAdd(&s_hist[q + i * kIxThreads < n ? code[i] : kCells + kCells / per + lane], 1);
-    } else {
-        for (int k = q; k < n; k += kIxThreads)
-            atomicAdd(&s_hist[hist_at((int)cell_code(g, xyz[k * 3 + 0], xyz[k * 3 + 1], xyz[k * 3 + 2]), per_shift)], 1);
-    }
-    __syncthreads();
-    EPNET_IX_STAMP(t_3);
-    int sum = 0;
-    for (int i = 0; i < per; ++i) sum += s_hist[hist_at(q * per + i, per_shift)];
-    const int incl = wave_inclusive_scan(sum);
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int base = incl - sum;
-    for (int w = 0; w < wave; ++w) base += s_part[w];
-    for (int i = 0; i < per; ++i) {
-        const int at = hist_at(q * per + i, per_shift);
-        const int c = s_hist[at];
-        s_hist[at] = base;
-        base += c;
-    }
-    __syncthreads();
-    EPNET_IX_STAMP(t_4);
-    auto bucket_box = [&](int p, const float4 v) {  // one wave handles one bucket at a time (all 64 lanes active)
-        const bool real = p < n;
-        const float cx_ = canonical(v.x), cy_ = canonical(v.y), cz_ = canonical(v.z);   // (quiet NaNs drop out of the box, as with fminf)
-        float mnx = real ? cx_ : 3.4e38f, mxx = real ? cx_ : -3.4e38f, mny = real ? cy_ : 3.4e38f, mxy = real ? cy_ : -3.4e38f,
-              mnz = real ? cz_ : 3.4e38f, mxz = real ? cz_ : -3.4e38f;
-        wave_box(mnx, mxx, mny, mxy, mnz, mxz);
-        if (lane == 0) {
-            float *bx = boxes + (p >> 6) * 6;
-            const bool any = mnx <= mxx;  // an all-padding bucket gets a box no ball can reach
-            bx[0] = any ? mnx : 3.0e38f; bx[1] = any ? mxx : 3.0e38f;
-            bx[2] = any ? mny : 3.0e38f; bx[3] = any ? mxy : 3.0e38f;
-            bx[4] = any ? mnz : 3.0e38f; bx[5] = any ? mxz : 3.0e38f;
-        }
-    };
-    const bool staged = in_regs && (np & 255) == 0;  // (three_nn's own index of a known set pads to 64 only: no whole-bucket quarters)
-    if (staged) {
-        // The sorted order goes through LDS, a quarter of the scene at a time: the points land in the staging buffer (scattered
-        // 16-byte LDS writes), leave for global memory as whole rows (the scattered 16-byte global stores this replaces were
-        // 46 % of the kernel: 4 M partial-line writes per 256 scenes) and give their bucket boxes on the way out (no read-back
-        // of what was just written: another 20 %).
-        float4 *s_stage = reinterpret_cast<float4 *>(s_hist + kCells + kCells / per + 64);
-        int pos[kIxPerThread];
-#pragma unroll
-        for (int i = 0; i < kIxPerThread; ++i) pos[i] = s_hist[code[i]] + rank[i];   // start of the cell + rank inside it
-        // a quarter of the scene per round; the 256-thread variant at most 512 points (8 KB): with 26 KB of LDS in all it still finds
-        // room on a CU that holds two 64 KB workgroups of a row gather -- at 34 KB it waited for the whole gather to drain (260 us)
-        // (a multiple of 64: np is a multiple of 256 here. A scene index has a power of two, three_nn's own index of a known set any
-        // multiple of 64 -- 2304, 2816, 3328, 3840 are not whole rounds of 512: the last round is shorter)
-        const int quarter = kIxThreads == 256 ? min(np >> 2, 512) : np >> 2;
-        for (int h = 0; h * quarter < np; ++h) {
-            const int base = h * quarter, len = min(quarter, np - base);
-            for (int p = q; p < len; p += kIxThreads)   // padding rows: never inside a ball
-                if (base + p >= n) s_stage[p] = make_float4(3.0e38f, 3.0e38f, 3.0e38f, __int_as_float(-1));
-#pragma unroll
-            for (int i = 0; i < kIxPerThread; ++i) {
-                const int k = q + i * kIxThreads;
-                if (k < n && (unsigned)(pos[i] - base) < (unsigned)quarter)
-                    s_stage[pos[i] - base] = make_float4(px[i], py[i], pz[i], __int_as_float(k));
-            }
-            __syncthreads();
-            for (int p = q; p < len; p += kIxThreads) {
-                const float4 v = s_stage[p];
-                sorted[base + p] = v;
-                bucket_box(base + p, v);
-            }
-            __syncthreads();
-        }
-    } else {
-        if (in_regs) {
-#pragma unroll
-            for (int i = 0; i < kIxPerThread; ++i) {
-                const int k = q + i * kIxThreads;
-                if (k < n) sorted[s_hist[code[i]] + rank[i]] = make_float4(px[i], py[i], pz[i], __int_as_float(k));
-            }
-        } else {
-            for (int k = q; k < n; k += kIxThreads) {
-                const float x = xyz[k * 3 + 0], y = xyz[k * 3 + 1], z = xyz[k * 3 + 2];
-                const int pos = atomicAdd(&s_hist[hist_at((int)cell_code(g, x, y, z), per_shift)], 1);
-                sorted[pos] = make_float4(x, y, z, __int_as_float(k));
-            }
-        }
-        for (int p = n + q; p < np; p += kIxThreads)  // padding: never inside a ball
-            sorted[p] = make_float4(3.0e38f, 3.0e38f, 3.0e38f, __int_as_float(-1));
-        __threadfence_block();
-        __syncthreads();  // the scattered points are read back by other waves of this workgroup below
-        for (int p = q; p < np; p += kIxThreads) bucket_box(p, sorted[p]);
-    }
 #ifdef EPNET_IX_STATS
-    {
-        EPNET_IX_STAMP(t_6);
-        if (q == 0) {
-            atomicAdd(&g_ix_stats[0], t_1 - t_0); atomicAdd(&g_ix_stats[1], t_2 - t_1); atomicAdd(&g_ix_stats[2], t_3 - t_2);
-            atomicAdd(&g_ix_stats[3], t_4 - t_3); atomicAdd(&g_ix_stats[4], t_6 - t_4);
-            atomicAdd(&g_ix_stats[7], 1ull);
-        }
-    }
+    unsigned long long *const ix_stats = g_ix_stats;
+#else
+    unsigned long long *const ix_stats = nullptr;
 #endif
-    if (!qboxes) return;
-    // second level: one box per 4 consecutive buckets (256 sorted points)
-    qboxes += (size_t)blockIdx.x * (np / 256) * 6;
-    __threadfence_block();
-    __syncthreads();
-    for (int g = q; g < np / 256; g += kIxThreads) {
-        float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-        for (int k = 0; k < 4; ++k) {
-            const float *bx = boxes + (g * 4 + k) * 6;
-            if (bx[0] < 3.0e38f)  // not an all-padding bucket
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    mn[a] = fminf(mn[a], bx[2 * a]);
-                    mx[a] = fmaxf(mx[a], bx[2 * a + 1]);
-                }
-        }
-        const bool any = mn[0] <= mx[0];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            qboxes[g * 6 + 2 * a] = any ? mn[a] : 3.0e38f;
-            qboxes[g * 6 + 2 * a + 1] = any ? mx[a] : 3.0e38f;
-        }
-    }
+    // (the 256-thread kernel stages at most 512 rows: see scene_index_build_block)
+    scene_index_build_block<kIxThreads, BITS, 16, kIxThreads == 256 ? 512 : 0, false>(s_hist, s_box, s_part, n, np, xyz, sorted, boxes, qboxes,
+                                                                                      n_src, src_idx, gathered, ix_stats);
 }
 
 constexpr int kQThreads = 256;
@@ -864,6 +653,9 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
         scan_pairs(__ballot(n0), __ballot(n1), [](int, int bit) { return bit; });
     } else {
         const int nq = np >> 8;
+        // every word of the two quad lists is a quad of this scene from here on (see the bucket-box pass)
+        s_quads[wave][0][lane] = 0;
+        s_quads[wave][1][lane] = 0;
         for (int q0 = 0; q0 < nq; q0 += 64) {
             const int qd = q0 + lane;
             // (a lane past the last quad tests the last one again and drops the answer: no branch around the loads, and the ballots
@@ -879,13 +671,15 @@ __global__ __launch_bounds__(kQThreads) void bq_query2_kernel(int np, int m, BqS
             const int nmine = half ? nq1 : nq0;
             for (int s0 = 0; s0 < max(nq0, nq1); s0 += 8) {  // 8 candidate quads of each centre per round
                 const int slot = s0 + ((lane & 31) >> 2);
-                int bid = 0;
-                bool bnear = false;
-                if (slot < nmine) {
-                    bid = s_quads[wave][half][slot] * 4 + (lane & 3);
-                    bnear = box_near(boxes + __umul24(bid, 6), hx, hy, hz, r2max);
-                }
-                const unsigned long long cand = __builtin_amdgcn_ballot_w64(bnear);
+                // no branch around the loads, and the ballot straight from the compare: a lane past its centre's list reads the list's
+                // last entry again (one address for all of them) and drops the answer. The unsigned minimum leaves `slot` itself for
+                // an EMPTY list -- a word of the list that holds a quad of this scene all the same: zero, or what an earlier round of
+                // the walk left (the lists are initialised above)
+                const unsigned sl = min((unsigned)slot, (unsigned)(nmine - 1));
+                const int bid = s_quads[wave][half][sl] * 4 + (lane & 3);
+                // (two ballots, each of its compare, and a scalar AND: the ballot of `near && mine` goes through a 0 / 1 register)
+                const unsigned long long cand = __builtin_amdgcn_ballot_w64(box_near(boxes + __umul24(bid, 6), hx, hy, hz, r2max)) &
+                                                __builtin_amdgcn_ballot_w64(slot < nmine);
                 scan_pairs(cand & 0xFFFFFFFFull, cand >> 32,
                            [&](int e, int bit) { return __builtin_amdgcn_readlane(bid, bit + 32 * e); });
             }

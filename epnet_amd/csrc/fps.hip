@@ -402,14 +402,14 @@ __device__ __forceinline__ void set_rank(VH &rk2, int j, unsigned r) {  // j is 
 // (distance bits << 32 | (0x3FFF - rank) << 10 | thread): the larger distance wins, equal distances go to the
 // smaller reference rank -- and after the round's single barrier the winner is read back with two
 // dependent LDS loads (key, then that thread's coordinates), no cross-lane reduction at all.
+// LDS comes from the caller (s_key: 3 keys, s_rec: one record slot per thread and round parity, s_idx: kIdxBufP ints), so that a
+// kernel with an epilogue of its own can lay the epilogue's LDS over them (fps_indexed_kernel).
 template <int kW, int PPT, typename VF, typename VI, typename VH>
-__device__ __forceinline__ void fps_rounds(int m, const VF &x, const VF &y, const VF &z, VI &t, const VH &rk2,
+__device__ __forceinline__ void fps_rounds(unsigned long long *s_key, float4 (*s_rec)[64 * kW], int *s_idx, int m, const VF &x,
+                                           const VF &y, const VF &z, VI &t, const VH &rk2,
                                            float cx, float cy, float cz, int *__restrict__ idxs,
                                            int *__restrict__ tie_free = nullptr, int known = 0,
                                            const float *__restrict__ xyz_in_order = nullptr, int detect_upto = 0x7fffffff) {
-    __shared__ unsigned long long s_key[3];
-    __shared__ float4 s_rec[2][64 * kW];  // one record slot per thread
-    __shared__ int s_idx[kIdxBufP];
     const int q = threadIdx.x;
     const int lane = q & 63, wave = q >> 6;
     const int sub = lane & (PPT - 1);  // the slot this lane summarises (for its own part)
@@ -640,6 +640,9 @@ __global__ __launch_bounds__(64 * kW) void fps_pruned_kernel(int n, int m, const
     unsigned short *perm = reinterpret_cast<unsigned short *>(s_dyn + kCells + kCells / (kCells / kT) + 64);
     __shared__ int s_part[16];
     __shared__ float s_box[6][16];
+    __shared__ unsigned long long s_key[3];
+    __shared__ float4 s_rec[2][64 * kW];
+    __shared__ int s_idx[kIdxBufP];
     const int q = threadIdx.x;
     const int lane = q & 63, wave = q >> 6;
     xyz += (size_t)blockIdx.x * n * 3;
@@ -678,7 +681,7 @@ __global__ __launch_bounds__(64 * kW) void fps_pruned_kernel(int n, int m, const
             set_rank(rk2, j, 0xFFFFu);
         }
     }
-    fps_rounds<kW, PPT>(m, x, y, z, t, rk2, xyz[0], xyz[1], xyz[2], idxs, prefix_out ? prefix_out + blockIdx.x : nullptr, 0,
+    fps_rounds<kW, PPT>(s_key, s_rec, s_idx, m, x, y, z, t, rk2, xyz[0], xyz[1], xyz[2], idxs, prefix_out ? prefix_out + blockIdx.x : nullptr, 0,
                         nullptr, prefix_cap);
     if (temp) {
 #pragma unroll
@@ -689,6 +692,16 @@ __global__ __launch_bounds__(64 * kW) void fps_pruned_kernel(int n, int m, const
     }
 }
 
+// The epilogue of fps_indexed_kernel: a function of its own (not inlined), so that its registers are allocated apart from the
+// round loop's -- two sampling waves of 200 VGPRs plus two gather waves per SIMD is what the pipelined schedule rests on.
+template <int kT, int BITS, int kPer, int kStage>
+__device__ __attribute__((noinline)) void fps_index_epilogue(int *s_hist, float (*s_box)[16], int *s_part, int m, int np,
+                                                             const float *xyz, float4 *sorted, float *boxes, float *qboxes, int n_src,
+                                                             const int *src_idx, float *gathered) {
+    scene_index_build_block<kT, BITS, kPer, kStage, true>(s_hist, s_box, s_part, m, np, xyz, sorted, boxes, qboxes, n_src, src_idx,
+                                                          gathered);
+}
+
 // Same rounds over a scene index built beforehand (spatial.h: cell-sorted float4 copy x, y, z, original index;
 // padding entries carry index -1). Needs no dynamic LDS, so it shares a CU with the bandwidth-bound kernels.
 template <int kW, int PPT>
@@ -696,11 +709,31 @@ __global__ __launch_bounds__(64 * kW) void fps_indexed_kernel(int n, int m, cons
                                                               float *__restrict__ temp, int *__restrict__ idxs,
                                                               const int *__restrict__ prefix_in,
                                                               int *__restrict__ prefix_out, const float *__restrict__ xyz,
-                                                              int prefix_cap, int prologue_init) {
+                                                              int prefix_cap, int prologue_init, void *next_index,
+                                                              float *__restrict__ new_xyz) {
     typedef float vecf __attribute__((ext_vector_type(PPT)));
     typedef int veci __attribute__((ext_vector_type(PPT)));
     constexpr int NP = 64 * kW * PPT;
-    __shared__ float s_first[4];
+    // ONE LDS array. The rounds' part: records, index buffer, keys, the first sample. The 512-thread kernel's epilogue (below) lays
+    // the next level's index build over it once the rounds are through: histogram, staging rows, box and scan partials.
+    constexpr bool kEpilogue = kW == 8;
+    constexpr int kRecAt = 0, kIdxAt = kRecAt + 2 * 64 * kW * 16, kKeyAt = kIdxAt + kIdxBufP * 4, kFirstAt = kKeyAt + 32,
+                  kRoundsBytes = kFirstAt + 16;
+    constexpr int kIxBits = 12, kIxPer = 8, kIxStage = 512;   // 512 threads x 8 points: m <= 4096
+    constexpr int kIxHistWords = (1 << kIxBits) + (1 << kIxBits) / ((1 << kIxBits) / (64 * kW)) + 64;
+    constexpr int kStageAt = kIxHistWords * 4, kBoxAt = kStageAt + kIxStage * 16, kPartAt = kBoxAt + 6 * 16 * 4,
+                  kIxBytes = kEpilogue ? kPartAt + 16 * 4 : 0;
+    // what only the epilogue needs waits in LDS behind the rounds' part (the kernel has no scalar registers to spare across the round
+    // loops: kept in SGPRs they were spilled to lanes of a 201st VGPR)
+    constexpr int kArgsAt = kRoundsBytes;
+    static_assert(kStageAt % 16 == 0 && kIxBytes <= 32768, "the sampling workgroup shares its CU with two 64 KB row gathers");
+    static_assert(!kEpilogue || kArgsAt + 32 <= kIxBytes, "epilogue arguments");
+    __shared__ __attribute__((aligned(16))) unsigned char s_lds[kRoundsBytes > kIxBytes ? kRoundsBytes : kIxBytes];
+    unsigned long long *const s_key = reinterpret_cast<unsigned long long *>(s_lds + kKeyAt);
+    float4(*const s_rec)[64 * kW] = reinterpret_cast<float4(*)[64 * kW]>(s_lds + kRecAt);
+    int *const s_idx = reinterpret_cast<int *>(s_lds + kIdxAt);
+    float *const s_first = reinterpret_cast<float *>(s_lds + kFirstAt);
+    unsigned long long *const s_args = reinterpret_cast<unsigned long long *>(s_lds + kArgsAt);
     const int q = threadIdx.x;
     const int lane = q & 63, wave = q >> 6;
     const int known = prefix_in ? prefix_in[blockIdx.x] : 0;
@@ -734,14 +767,45 @@ __global__ __launch_bounds__(64 * kW) void fps_indexed_kernel(int n, int m, cons
             set_rank(rk2, j, 0xFFFFu);
         }
     }
+    if constexpr (kEpilogue) {
+        if (q == 0) {
+            s_args[0] = (unsigned long long)next_index;
+            s_args[1] = (unsigned long long)new_xyz;
+            s_args[2] = (unsigned long long)xyz;
+            s_args[3] = (unsigned long long)(unsigned)n;
+        }
+    }
     __syncthreads();
-    fps_rounds<kW, PPT>(m, x, y, z, t, rk2, s_first[0], s_first[1], s_first[2], idxs, prefix_out ? prefix_out + blockIdx.x : nullptr,
-                        known, xyz ? xyz + (size_t)blockIdx.x * n * 3 : nullptr, prefix_cap);
+    fps_rounds<kW, PPT>(s_key, s_rec, s_idx, m, x, y, z, t, rk2, s_first[0], s_first[1], s_first[2], idxs,
+                        prefix_out ? prefix_out + blockIdx.x : nullptr, known, xyz ? xyz + (size_t)blockIdx.x * n * 3 : nullptr,
+                        prefix_cap);
     if (temp) {
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
             const unsigned r = rank_of(rk2, j);
             if (r != 0xFFFFu) temp[unrank14(r)] = __int_as_float(t[j]);
+        }
+    }
+    if constexpr (kEpilogue) {
+        // The next level's preparation, by the workgroup that has just picked its points: the m centres are gathered (new_xyz) and
+        // their scene index is built (what epnet_scene_index_build_gathered does in a dispatch of its own): one dispatch less on the
+        // sampling chain, and every scene starts as soon as ITS rounds end. Beside the wide kernels of the pipelined stack the build
+        // costs this kernel about what it cost as a dispatch (0.06 ms). The priority stays raised, as in bq_index_kernel.
+        // next_index != NULL (block-uniform) implies 1024 <= m <= 4096 and no prefix_in (fps_over_index).
+        void *const next_index_ = (void *)s_args[0];
+        if (next_index_) {
+            float *const new_xyz_ = (float *)s_args[1];
+            const float *const xyz_ = (const float *)s_args[2];
+            const int n_ = (int)s_args[3];
+            __threadfence_block();   // wave 0's last flush of idxs
+            __syncthreads();         // ... and nobody reads the rounds' LDS (or the arguments above) any more
+            const int np2 = m <= 2048 ? 2048 : 4096;   // scene_index_np(m)
+            float4 *const sorted2 = reinterpret_cast<float4 *>(next_index_);
+            float *const boxes2 = reinterpret_cast<float *>(sorted2 + (size_t)gridDim.x * np2);
+            float *const qboxes2 = boxes2 + (size_t)gridDim.x * (np2 / 64) * 6;
+            fps_index_epilogue<64 * kW, kIxBits, kIxPer, kIxStage>(
+                reinterpret_cast<int *>(s_lds), reinterpret_cast<float(*)[16]>(s_lds + kBoxAt), reinterpret_cast<int *>(s_lds + kPartAt),
+                m, np2, xyz_, sorted2, boxes2, qboxes2, n_, idxs - (size_t)blockIdx.x * m, new_xyz_);
         }
     }
 }
@@ -1228,9 +1292,19 @@ static void launch_gather_centres(int b, int n, int m, const float *xyz, const i
 // shared by the two entry points below; new_xyz may be NULL
 static int fps_over_index(int b, int n, int m, const float *xyz, void *index, size_t index_bytes, float *temp, int *idx,
                           float *new_xyz, hipStream_t s, const int *skip = nullptr, int *prefix_out = nullptr,
-                          int prefix_cap = 0x7fffffff) {
+                          int prefix_cap = 0x7fffffff, void *next_index = nullptr, size_t next_index_bytes = 0) {
     const size_t need = scene_index_bytes(b, n);
     int rc;
+    // next_index: the scene index of the m centres is wanted as well (epnet_sample_centres_chain_index). The 512-thread indexed
+    // kernel builds it in its epilogue, 8 centres per thread: 1024 <= m <= 4096, and every scene must run the kernel's tail (no
+    // known prefixes: a scene taking the identity leaves early). Everything else: the dispatch of epnet_scene_index_build_gathered.
+    if (next_index) {
+        const size_t need2 = scene_index_bytes(b, m);
+        EPNET_REQUIRE(need2 != 0 && m <= 16384 && new_xyz && xyz && idx && b <= 65535);
+        if (next_index_bytes < need2) return EPNET_ENOMEM;
+        if (((uintptr_t)next_index & 15) != 0) return EPNET_EINVAL;
+    }
+    bool built_next = false;
     const bool plain = need == 0 || !index || n <= 1024 || m <= 1 || (n > 16384 && !temp);
     int fold_init = -1;   // >= 0: the known prefixes / the tie-free counts still need their initial treatment (fps_prologue)
     bool wrote_centres = false;   // by the sampling kernel itself (fps_wave_kernel)
@@ -1265,9 +1339,12 @@ static int fps_over_index(int b, int n, int m, const float *xyz, void *index, si
         } else {
             // (the centres come from the small gather below: written by the sampling kernel itself they cost wave 0 an LDS write
             // per round and 12 KB more LDS, 1.7 % on one scene and 5 % in the software-pipelined stack -- more than the launch)
+            const bool epilogue = next_index && !skip && scene_index_np(n) == 16384 && m >= 1024 && m <= 4096;
+            void *const epi_index = epilogue ? next_index : nullptr;
 #define EPNET_FPS_INDEXED(W_, P_)                                                                                                     \
     hipLaunchKernelGGL((pruned::fps_indexed_kernel<W_, P_>), grid, dim3(64 * W_), 0, s, n, m, sorted, temp, idx, skip, prefix_out, xyz, \
-                       prefix_cap, fold_init)
+                       prefix_cap, fold_init, epi_index, new_xyz)
+            built_next = epilogue;
             switch (scene_index_np(n)) {
                 case 2048: EPNET_FPS_INDEXED(4, 8); break;
                 case 4096: EPNET_FPS_INDEXED(4, 16); break;
@@ -1278,7 +1355,14 @@ static int fps_over_index(int b, int n, int m, const float *xyz, void *index, si
         }
         rc = check_launch("furthest_point_sampling");
     }
-    if (rc || !new_xyz || wrote_centres) return rc;
+    if (rc || built_next) return rc;
+    if (next_index) {   // gather + index build in one dispatch (a sampling kernel that wrote the centres itself wrote the same rows)
+        const int np2 = scene_index_np(m);
+        float4 *sorted2 = (float4 *)next_index;
+        float *boxes2 = (float *)(sorted2 + (size_t)b * np2);
+        return spatial_index_launch(b, m, np2, xyz, sorted2, boxes2, boxes2 + (size_t)b * (np2 / 64) * 6, s, n, idx, new_xyz);
+    }
+    if (!new_xyz || wrote_centres) return rc;
     if (m == 0) return EPNET_OK;
     EPNET_REQUIRE(xyz && b <= 65535);
     launch_gather_centres(b, n, m, xyz, idx, new_xyz, s);
@@ -1321,4 +1405,21 @@ extern "C" int epnet_sample_centres_chain(int b, int n, int m, const float *xyz,
     if (m > n) prefix_in = nullptr;  // more samples than points: the sequence repeats points, nothing is known
     return fps_over_index(b, n, m, xyz, index, index_bytes, temp, idx, new_xyz, (hipStream_t)stream, prefix_in, prefix_out,
                           prefix_cap);
+}
+
+// epnet_sample_centres_chain AND the scene index of the m centres (epnet_scene_index_build_gathered on idx: what the next level of
+// the pyramid starts with) into next_index, a buffer of epnet_scene_index_bytes(b, m) bytes; 1024 <= m <= 16384, new_xyz required.
+// For 8192 < n <= 16384, 1024 <= m <= 4096 and no prefix_in the sampling workgroup of a scene gathers its centres and builds their
+// index itself, as the epilogue of its rounds -- no dispatch between the sampling and the next level's; every other shape runs the
+// two launches, with the same results. (The order of the points INSIDE a grid cell of an index is unspecified either way.)
+extern "C" int epnet_sample_centres_chain_index(int b, int n, int m, const float *xyz, void *index, size_t index_bytes,
+                                                float *temp, int *idx, float *new_xyz, const int *prefix_in, int *prefix_out,
+                                                int prefix_cap, void *next_index, size_t next_index_bytes,
+                                                epnet_stream_t stream) {
+    EPNET_REQUIRE(b >= 0 && n >= 1 && m >= 0);
+    if (b == 0 || m == 0) return EPNET_OK;
+    EPNET_REQUIRE(xyz && idx && new_xyz && next_index);
+    if (m > n) prefix_in = nullptr;
+    return fps_over_index(b, n, m, xyz, index, index_bytes, temp, idx, new_xyz, (hipStream_t)stream, prefix_in, prefix_out,
+                          prefix_cap, next_index, next_index_bytes);
 }

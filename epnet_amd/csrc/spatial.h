@@ -2,6 +2,7 @@
 // The spatial order only decides WHICH work can be skipped; results never depend on it.
 #pragma once
 #include "common.h"
+#include "dpp.h"
 
 namespace epnet {
 
@@ -212,6 +213,242 @@ inline size_t scene_index_bytes(int b, int n) {
 inline float *scene_index_sampling_scratch(int b, int n, void *index) {
     const size_t np = (size_t)scene_index_np(n);
     return (float *)((char *)index + (size_t)b * (np * sizeof(float4) + (np / 64 + np / 256) * 6 * sizeof(float)));
+}
+
+// ---- the index build of one scene by one workgroup (bq_index_kernel in ball_query.hip; the epilogue of a sampling kernel in
+// fps.hip, which builds the NEXT level's index from the centres it has just picked) ------------------------------------
+// kIxThreads threads, 2^BITS grid cells, kIxPerThread points per thread held in registers (kIxThreads * kIxPerThread >= n for the
+// one-read path; kRegsOnly: the caller guarantees that, the re-reading paths are not compiled), kStageCap: rows of the staging
+// buffer (0: a quarter of the scene). LDS comes from the caller: s_hist = (2^BITS + 2^BITS / per + 64) ints of histogram followed,
+// 16-byte aligned, by the staging rows; s_box 6 x 16 floats, s_part 16 ints. All threads of the workgroup call it; blockIdx.x is
+// the scene. src_idx / gathered (in-register path only): see bq_index_kernel.
+#ifdef EPNET_IX_STATS  // diagnostic build only (profiles/micro/ix_stats.py): phase counters of the index build (wave 0)
+#define EPNET_IX_STAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
+#else
+#define EPNET_IX_STAMP(var)
+#endif
+
+template <int kIxThreads, int BITS, int kIxPerThread, int kStageCap, bool kRegsOnly>
+__device__ __forceinline__ void scene_index_build_block(int *s_hist, float (*s_box)[16], int *s_part, int n, int np,
+                                                        const float *__restrict__ xyz, float4 *__restrict__ sorted,
+                                                        float *__restrict__ boxes, float *__restrict__ qboxes, int n_src,
+                                                        const int *__restrict__ src_idx, float *__restrict__ gathered,
+                                                        unsigned long long *ix_stats = nullptr) {
+    constexpr int kCells = 1 << BITS;
+    const int q = threadIdx.x, lane = q & 63, wave = q >> 6;
+    // src_idx (n <= kIxThreads * kIxPerThread only): the scene's points are rows src_idx[0 .. n) of a cloud of n_src points -- the centres a
+    // sampling has just picked -- and are written out in that order as well (gathered): the centre gather of an SA level and the
+    // index build of the next one in one dispatch
+    xyz += (size_t)blockIdx.x * (src_idx ? n_src : n) * 3;
+    if (src_idx) {
+        src_idx += (size_t)blockIdx.x * n;
+        gathered += (size_t)blockIdx.x * n * 3;
+    }
+    sorted += (size_t)blockIdx.x * np;
+    boxes += (size_t)blockIdx.x * (np / 64) * 6;
+    // counting sort by cell, scattering the points (with their original index) straight to global memory.
+    // Up to kIxPerThread points per thread the cloud is read ONCE into registers (bounding box, cell codes and the
+    // scatter all work from there); bigger clouds re-read it per phase.
+    constexpr int per = kCells / kIxThreads;
+    constexpr int per_shift = per == 16 ? 4 : per == 8 ? 3 : per == 4 ? 2 : -1;
+    static_assert(per_shift > 0, "scan layout");
+    const bool in_regs = kRegsOnly || n <= kIxThreads * kIxPerThread;  // block-uniform
+    float px[kIxPerThread], py[kIxPerThread], pz[kIxPerThread];
+    float lo[3], ext[3];
+    EPNET_IX_STAMP(t_0);
+    if (in_regs) {
+        float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+        // all of a thread's points are requested before the first one is used, and nothing below branches on `k < n`: with the
+        // box update under an `if` every iteration was a basic block of its own and its load was waited for before the next
+        // was issued -- 16 serial trips to HBM at the head of the sampling chain of every level
+        int row[kIxPerThread];
+#pragma unroll
+        for (int i = 0; i < kIxPerThread; ++i) {
+            const int k = q + i * kIxThreads;
+            const int kk = k < n ? k : 0;
+            row[i] = src_idx ? src_idx[kk] : kk;
+        }
+#pragma unroll
+        for (int i = 0; i < kIxPerThread; ++i) {
+            px[i] = xyz[row[i] * 3 + 0];
+            py[i] = xyz[row[i] * 3 + 1];
+            pz[i] = xyz[row[i] * 3 + 2];
+        }
+        if (src_idx) {
+#pragma unroll
+            for (int i = 0; i < kIxPerThread; ++i) {
+                const int k = q + i * kIxThreads;
+                if (k < n) {
+                    gathered[k * 3 + 0] = px[i];
+                    gathered[k * 3 + 1] = py[i];
+                    gathered[k * 3 + 2] = pz[i];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kIxPerThread; ++i) {
+            const bool ok = q + i * kIxThreads < n;
+            mn[0] = fminf(mn[0], ok ? px[i] : 3.4e38f); mx[0] = fmaxf(mx[0], ok ? px[i] : -3.4e38f);
+            mn[1] = fminf(mn[1], ok ? py[i] : 3.4e38f); mx[1] = fmaxf(mx[1], ok ? py[i] : -3.4e38f);
+            mn[2] = fminf(mn[2], ok ? pz[i] : 3.4e38f); mx[2] = fmaxf(mx[2], ok ? pz[i] : -3.4e38f);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float l = wave_minf_all(mn[a]), h = wave_maxf_all(mx[a]);
+            if (lane == 0) {
+                s_box[a][wave] = l;
+                s_box[3 + a][wave] = h;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            float l = s_box[a][0], h = s_box[3 + a][0];
+            for (int w = 1; w < kIxThreads / 64; ++w) {
+                l = fminf(l, s_box[a][w]);
+                h = fmaxf(h, s_box[3 + a][w]);
+            }
+            lo[a] = l;
+            ext[a] = h - l;
+        }
+    } else {
+        block_bbox3(xyz, n, s_box, lo, ext);
+    }
+    const CellGrid g = make_cell_grid(lo, ext, BITS);
+    EPNET_IX_STAMP(t_1);
+    for (int i = q; i < kCells + kCells / per + 64; i += kIxThreads) s_hist[i] = 0;
+    __syncthreads();
+    EPNET_IX_STAMP(t_2);
+    // in_regs: the histogram pass keeps what its atomics return -- a point's rank inside its cell -- so the scatter below needs
+    // no second round of atomics on the same (hot: a cell next to the sensor holds hundreds of points) words: 46 % of the kernel
+    int code[kIxPerThread], rank[kIxPerThread];
+    if (in_regs) {
+#pragma unroll
+        for (int i = 0; i < kIxPerThread; ++i) code[i] = hist_at((int)cell_code(g, px[i], py[i], pz[i]), per_shift);
+#pragma unroll
+        for (int i = 0; i < kIxPerThread; ++i)   // (a slot beyond n counts on one of the 64 spare words behind the histogram)
+            rank[i] = atomicAdd(&s_hist[q + i * kIxThreads < n ? code[i] : kCells + kCells / per + lane], 1);
+    } else {
+        for (int k = q; k < n; k += kIxThreads)
+            atomicAdd(&s_hist[hist_at((int)cell_code(g, xyz[k * 3 + 0], xyz[k * 3 + 1], xyz[k * 3 + 2]), per_shift)], 1);
+    }
+    __syncthreads();
+    EPNET_IX_STAMP(t_3);
+    int sum = 0;
+    for (int i = 0; i < per; ++i) sum += s_hist[hist_at(q * per + i, per_shift)];
+    const int incl = wave_inclusive_scan(sum);
+    if (lane == 63) s_part[wave] = incl;
+    __syncthreads();
+    int base = incl - sum;
+    for (int w = 0; w < wave; ++w) base += s_part[w];
+    for (int i = 0; i < per; ++i) {
+        const int at = hist_at(q * per + i, per_shift);
+        const int c = s_hist[at];
+        s_hist[at] = base;
+        base += c;
+    }
+    __syncthreads();
+    EPNET_IX_STAMP(t_4);
+    auto bucket_box = [&](int p, const float4 v) {  // one wave handles one bucket at a time (all 64 lanes active)
+        const bool real = p < n;
+        const float cx_ = canonical(v.x), cy_ = canonical(v.y), cz_ = canonical(v.z);   // (quiet NaNs drop out of the box, as with fminf)
+        float mnx = real ? cx_ : 3.4e38f, mxx = real ? cx_ : -3.4e38f, mny = real ? cy_ : 3.4e38f, mxy = real ? cy_ : -3.4e38f,
+              mnz = real ? cz_ : 3.4e38f, mxz = real ? cz_ : -3.4e38f;
+        wave_box(mnx, mxx, mny, mxy, mnz, mxz);
+        if (lane == 0) {
+            float *bx = boxes + (p >> 6) * 6;
+            const bool any = mnx <= mxx;  // an all-padding bucket gets a box no ball can reach
+            bx[0] = any ? mnx : 3.0e38f; bx[1] = any ? mxx : 3.0e38f;
+            bx[2] = any ? mny : 3.0e38f; bx[3] = any ? mxy : 3.0e38f;
+            bx[4] = any ? mnz : 3.0e38f; bx[5] = any ? mxz : 3.0e38f;
+        }
+    };
+    const bool staged = kRegsOnly || (in_regs && (np & 255) == 0);  // (three_nn's own index of a known set pads to 64 only: no whole-bucket quarters)
+    if (staged) {
+        // The sorted order goes through LDS, a quarter of the scene at a time: the points land in the staging buffer (scattered
+        // 16-byte LDS writes), leave for global memory as whole rows (the scattered 16-byte global stores this replaces were
+        // 46 % of the kernel: 4 M partial-line writes per 256 scenes) and give their bucket boxes on the way out (no read-back
+        // of what was just written: another 20 %).
+        float4 *s_stage = reinterpret_cast<float4 *>(s_hist + kCells + kCells / per + 64);
+        int pos[kIxPerThread];
+#pragma unroll
+        for (int i = 0; i < kIxPerThread; ++i) pos[i] = s_hist[code[i]] + rank[i];   // start of the cell + rank inside it
+        // a quarter of the scene per round; with kStageCap (the 256-thread kernel, a sampling kernel's epilogue) at most 512 points (8 KB): with 26 KB of LDS in all it still finds
+        // room on a CU that holds two 64 KB workgroups of a row gather -- at 34 KB it waited for the whole gather to drain (260 us)
+        // (a multiple of 64: np is a multiple of 256 here. A scene index has a power of two, three_nn's own index of a known set any
+        // multiple of 64 -- 2304, 2816, 3328, 3840 are not whole rounds of 512: the last round is shorter)
+        const int quarter = kStageCap ? min(np >> 2, kStageCap) : np >> 2;
+        for (int h = 0; h * quarter < np; ++h) {
+            const int base = h * quarter, len = min(quarter, np - base);
+            for (int p = q; p < len; p += kIxThreads)   // padding rows: never inside a ball
+                if (base + p >= n) s_stage[p] = make_float4(3.0e38f, 3.0e38f, 3.0e38f, __int_as_float(-1));
+#pragma unroll
+            for (int i = 0; i < kIxPerThread; ++i) {
+                const int k = q + i * kIxThreads;
+                if (k < n && (unsigned)(pos[i] - base) < (unsigned)quarter)
+                    s_stage[pos[i] - base] = make_float4(px[i], py[i], pz[i], __int_as_float(k));
+            }
+            __syncthreads();
+            for (int p = q; p < len; p += kIxThreads) {
+                const float4 v = s_stage[p];
+                sorted[base + p] = v;
+                bucket_box(base + p, v);
+            }
+            __syncthreads();
+        }
+    } else {
+        if (in_regs) {
+#pragma unroll
+            for (int i = 0; i < kIxPerThread; ++i) {
+                const int k = q + i * kIxThreads;
+                if (k < n) sorted[s_hist[code[i]] + rank[i]] = make_float4(px[i], py[i], pz[i], __int_as_float(k));
+            }
+        } else {
+            for (int k = q; k < n; k += kIxThreads) {
+                const float x = xyz[k * 3 + 0], y = xyz[k * 3 + 1], z = xyz[k * 3 + 2];
+                const int pos = atomicAdd(&s_hist[hist_at((int)cell_code(g, x, y, z), per_shift)], 1);
+                sorted[pos] = make_float4(x, y, z, __int_as_float(k));
+            }
+        }
+        for (int p = n + q; p < np; p += kIxThreads)  // padding: never inside a ball
+            sorted[p] = make_float4(3.0e38f, 3.0e38f, 3.0e38f, __int_as_float(-1));
+        __threadfence_block();
+        __syncthreads();  // the scattered points are read back by other waves of this workgroup below
+        for (int p = q; p < np; p += kIxThreads) bucket_box(p, sorted[p]);
+    }
+#ifdef EPNET_IX_STATS
+    {
+        EPNET_IX_STAMP(t_6);
+        if (q == 0 && ix_stats) {
+            atomicAdd(&ix_stats[0], t_1 - t_0); atomicAdd(&ix_stats[1], t_2 - t_1); atomicAdd(&ix_stats[2], t_3 - t_2);
+            atomicAdd(&ix_stats[3], t_4 - t_3); atomicAdd(&ix_stats[4], t_6 - t_4);
+            atomicAdd(&ix_stats[7], 1ull);
+        }
+    }
+#endif
+    if (!qboxes) return;
+    // second level: one box per 4 consecutive buckets (256 sorted points)
+    qboxes += (size_t)blockIdx.x * (np / 256) * 6;
+    __threadfence_block();
+    __syncthreads();
+    for (int g = q; g < np / 256; g += kIxThreads) {
+        float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+        for (int k = 0; k < 4; ++k) {
+            const float *bx = boxes + (g * 4 + k) * 6;
+            if (bx[0] < 3.0e38f)  // not an all-padding bucket
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    mn[a] = fminf(mn[a], bx[2 * a]);
+                    mx[a] = fmaxf(mx[a], bx[2 * a + 1]);
+                }
+        }
+        const bool any = mn[0] <= mx[0];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            qboxes[g * 6 + 2 * a] = any ? mn[a] : 3.0e38f;
+            qboxes[g * 6 + 2 * a + 1] = any ? mx[a] : 3.0e38f;
+        }
+    }
 }
 
 // defined in ball_query.hip

@@ -267,6 +267,31 @@ def sample_centres_wrapper(b, n, m, points, index, idx, new_xyz, prefix_in=None,
     return 1
 
 
+@writes("idx", "new_xyz", "prefix_out", "next_index")
+def sample_centres_index_wrapper(b, n, m, points, index, idx, new_xyz, next_index, prefix_in=None, prefix_out=None, prefix_cap=0):
+    """sample_centres_wrapper (chained form) and scene_index_build_gathered_wrapper of its centres in one call: idx (B,M),
+    new_xyz (B,M,3) and the scene index of new_xyz in `next_index` (scene_index bytes of (b, m); 1024 <= m <= 16384). Where the
+    sampling kernel can, it builds the index in its own epilogue (include/epnet_ops.h: epnet_sample_centres_chain_index)"""
+    pp, pi, pn = dev_ptr(points, "points", _F), dev_ptr(idx, "idx", _I), dev_ptr(new_xyz, "new_xyz", _F)
+    need(points, b * n * 3, "points"); need(idx, b * m, "idx"); need(new_xyz, b * m * 3, "new_xyz")
+    px, nb = _index_args(index, points)
+    nx, nnb = _index_args(next_index, points)
+    if nx is None:
+        raise RuntimeError("sample_centres_index_wrapper needs the next level's index buffer")
+    pin = dev_ptr(prefix_in, "prefix_in", _I) if prefix_in is not None else None
+    pout = dev_ptr(prefix_out, "prefix_out", _I) if prefix_out is not None else None
+    if prefix_in is not None:
+        need(prefix_in, b, "prefix_in")
+    if prefix_out is not None:
+        need(prefix_out, b, "prefix_out")
+    temp = None if 64 <= n <= 16384 else torch.full((b, n), 1e10, dtype=_F, device=points.device)
+    pt = None if temp is None else temp.data_ptr()
+    with on_device_of(points) as s:
+        _lib.check(_lib.lib().epnet_sample_centres_chain_index(b, n, m, pp, px, nb, pt, pi, pn, pin, pout, int(prefix_cap), nx, nnb, s),
+                   "sample_centres_index")
+    return 1
+
+
 @writes("idxs")
 def ball_query_multi_wrapper(b, n, m, radii, nsamples, new_xyz, xyz, index, idxs):
     """the ball queries of all scales of an MSG level in one launch (same results as one ball_query per scale)"""

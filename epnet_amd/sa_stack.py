@@ -106,7 +106,9 @@ class SAStack:
         #    stage G -> 3.18 - 3.26 with level 2's in S -> 3.11 - 3.13 with levels 2-4, once the scene index build had become
         #    0.05 ms shorter; all levels: 3.52, level 1 alone: 3.49; at 128 scenes stage S is the longer one: 2.62 -> 2.69, so
         #    not there, and
-        #    at 192 scenes 2.77 -> 2.88).
+        #    at 192 scenes 2.77 -> 2.88). Since the level-2 gather runs at the other levels' rate, level 2's queries are better off
+        #    back in stage G, in front of that gather, where they run beside the level-1 sampling instead of in S's tail: levels
+        #    3-4 only, below levels 2-4 in every one of 15 alternating rounds over three sessions, by 0.02 - 0.05 ms.
         # EPNET_SA_QUERIES_IN_S = 0: none, 1 (default): as above, 2: all levels; EPNET_SA_S_QUERY_LEVELS = "1,3": these (0-based)
         env_q = int(os.environ.get("EPNET_SA_QUERIES_IN_S", "1"))
         env_lv = os.environ.get("EPNET_SA_S_QUERY_LEVELS")
@@ -124,7 +126,7 @@ class SAStack:
         elif env_q == 2 or (env_q == 1 and with_fp):
             chosen = every
         elif env_q == 1 and batch * n >= 240 * 16384:
-            chosen = every - {0}
+            chosen = every - {0, 1}
         else:
             chosen = frozenset()
         self.s_query_levels = chosen & every
@@ -132,8 +134,13 @@ class SAStack:
         # levels 2.. of the pyramid sample the centres of the level above: with the chain of tie-free round counts handed from level
         # to level (epnet_sample_centres_chain) their rounds are skipped wherever the answer is known to be 0 .. m-1
         self.chain = bool(int(os.environ.get("EPNET_SA_CHAIN", "1"))) and fused_sampling
-        self.fuse_gather = bool(int(os.environ.get("EPNET_SA_FUSE_GATHER", "1")))   # centre gather inside the next level's index build
+        # the centre gather and the NEXT level's scene index: 1 (default) with the sampling in one call (epnet_sample_centres_chain_index:
+        # the level-1 sampling workgroups do both in their epilogue, no dispatch behind the level-1 FPS); 2: the gather inside the next
+        # level's index-build dispatch (epnet_scene_index_build_gathered, the default before the epilogue existed); 0: a gather and a
+        # build of their own
+        self.fuse_gather = int(os.environ.get("EPNET_SA_FUSE_GATHER", "1"))
         self._deferred = None
+        self._next_built = None   # (level, parity) whose index the sampling call of the level above has built
         # the level-1 sampling issued ahead of stage G's first kernel (both wait for the level-1 index only): its one-per-CU workgroups
         # find their registers before the wide kernels fill the CUs. 128 scenes 2.62 -> 2.57 ms, 256 scenes with every query in
         # stage G 3.52 -> 3.43; nothing once stage G starts with an LDS-staged gather (queries of level 2 in stage S: 3.21 = 3.22)
@@ -266,10 +273,13 @@ class SAStack:
         P = L["sets"][parity]
         lvl = self.levels.index(L)
         pending, self._deferred = self._deferred, None
+        built, self._next_built = self._next_built, None
         if pending is not None and pending[1:] == (lvl - 1, parity):   # cur_xyz has not been written yet: gather + index in one
             src_xyz, _, _ = pending
             prev = self.levels[lvl - 1]
             ext.scene_index_build_gathered_wrapper(b, prev["n"], n, src_xyz, prev["fps_idx_sets"][parity], cur_xyz, P["index"])
+        elif built == (lvl, parity):   # by the sampling call of the level above, with cur_xyz
+            pass
         elif P["index"] is not None and not index_built:
             ext.scene_index_build_wrapper(b, n, cur_xyz, P["index"])
         if self.fused_sampling:   # FPS + gather of the centres in one kernel (epnet_sample_centres)
@@ -281,10 +291,15 @@ class SAStack:
                 nxt_L = self.levels[lvl + 1] if lvl + 1 < len(self.levels) else None
                 defer = (defer_ok and self.fuse_gather and self.fused and nxt_L is not None
                          and nxt_L["sets"][parity]["index"] is not None and 1024 <= m <= 16384)
-                ext.sample_centres_wrapper(b, n, m, cur_xyz, P["index"], L["fps_idx_sets"][parity], None if defer else P["new_xyz"],
-                                           prefix_in, P["prefix"], nxt)
-                if defer:
-                    self._deferred = (cur_xyz, lvl, parity)
+                if defer and self.fuse_gather == 1:
+                    ext.sample_centres_index_wrapper(b, n, m, cur_xyz, P["index"], L["fps_idx_sets"][parity], P["new_xyz"],
+                                                     nxt_L["sets"][parity]["index"], prefix_in, P["prefix"], nxt)
+                    self._next_built = (lvl + 1, parity)
+                else:
+                    ext.sample_centres_wrapper(b, n, m, cur_xyz, P["index"], L["fps_idx_sets"][parity], None if defer else P["new_xyz"],
+                                               prefix_in, P["prefix"], nxt)
+                    if defer:
+                        self._deferred = (cur_xyz, lvl, parity)
             else:
                 ext.sample_centres_wrapper(b, n, m, cur_xyz, P["index"], L["fps_idx_sets"][parity], P["new_xyz"])
         else:                     # the reference module's sequence, op by op
@@ -471,10 +486,11 @@ class SAStack:
         forked = torch.cuda.Event()
         forked.record(main)
         # ---- S1 (this stream): the level-1 rounds of batch `step`
-        self._deferred = None
+        self._deferred = self._next_built = None
         self._sample_level(first, clouds[p], p, index_built=True, defer_ok=True)
         s1_deferred = self._deferred is not None   # (a property of the configuration: the same in every step)
-        self._deferred = None
+        s1_built = self._next_built is not None    # (likewise: level 2's index came out of the level-1 sampling call)
+        self._deferred = self._next_built = None
         # ---- G: groupings (and interpolation) of the batch of two steps before
         side.wait_event(forked)
         with torch.cuda.stream(side):
@@ -494,10 +510,11 @@ class SAStack:
         with torch.cuda.stream(third):
             # what S1 of the step before left undone: the level-1 centres are gathered by level 2's index build
             self._deferred = (clouds[q], 0, q) if s1_deferred else None
+            self._next_built = (1, q) if s1_built else None
             cur = first["sets"][q]["new_xyz"]
             for L in self.levels[1:]:
                 cur = self._sample_level(L, cur, q, defer_ok=True)
-            self._deferred = None
+            self._deferred = self._next_built = None
             if self.with_fp:
                 self._search_fp(clouds[q], q)
             self._queries_of(clouds[q], q)
@@ -554,10 +571,10 @@ class SAStack:
         (the "previous batch" = clouds[1]) reads valid centres and indices, never uninitialised memory"""
         for parity in range(self.ring):
             xyz = cur = clouds[parity]
-            self._deferred = None
+            self._deferred = self._next_built = None
             for L in self.levels:
                 cur = self._sample_level(L, cur, parity, defer_ok=True)
-            self._deferred = None
+            self._deferred = self._next_built = None
             if self.with_fp:
                 self._search_fp(xyz, parity)
             if self.s_query_levels:

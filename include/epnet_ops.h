@@ -316,6 +316,15 @@ int epnet_sample_centres(int b, int n, int m, const float *xyz, void *index, siz
 int epnet_sample_centres_chain(int b, int n, int m, const float *xyz, void *index, size_t index_bytes, float *temp,
                                int *idx, float *new_xyz, const int *prefix_in, int *prefix_out, int prefix_cap,
                                epnet_stream_t stream);
+/* epnet_sample_centres_chain followed by epnet_scene_index_build_gathered(b, n, m, xyz, idx, new_xyz, next_index, ...): the centres
+ * AND their scene index, which is what the next level of the pyramid starts with. next_index: epnet_scene_index_bytes(b, m) bytes,
+ * 16-byte aligned; 1024 <= m <= 16384; new_xyz is required. For 8192 < n <= 16384 over an index, 1024 <= m <= 4096 and
+ * prefix_in == NULL the sampling workgroup of a scene does both in the epilogue of its rounds (no dispatch in between: on a busy
+ * chip a small dispatch mostly waits for a place); every other shape issues the two launches. idx, new_xyz and prefix_out are the
+ * same bits either way; inside a grid cell of the index the order of the points is unspecified, as for every index build. */
+int epnet_sample_centres_chain_index(int b, int n, int m, const float *xyz, void *index, size_t index_bytes, float *temp,
+                                     int *idx, float *new_xyz, const int *prefix_in, int *prefix_out, int prefix_cap,
+                                     void *next_index, size_t next_index_bytes, epnet_stream_t stream);
 /* same contract as epnet_three_nn (interpolate_gpu.cu:55-74); known_index = scene index of `known` (NULL: plain
  * path), unknown_index = scene index of `unknown` or NULL */
 int epnet_three_nn_indexed(int b, int n, int m, const float *unknown, const float *known, const void *unknown_index,
