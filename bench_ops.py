@@ -4,7 +4,7 @@ iou3d (rotated overlap / IoU, both NMS flavours), roipool3d, three_nn / three_in
 gradient ops, at the shapes of the reference's rcnn_online step. One JSON line per op:
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
-    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only | --handover-only]
+    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only | --gt-aug-only | --handover-only]
 """
 import argparse
 import json
@@ -753,9 +753,89 @@ def kitti_eval_rows(args):
           flush=True)
 
 
+def gt_aug_rows(args, report, timeit_pair):
+    """GT-database augmentation (epnet_amd/gt_aug_layer.py: placement, points, sampling -- three calls, six launches) at 1 / 2 / 16 /
+    256 scenes of 122 880 raw points -> 16384 on a synthetic database, the augmentation applied in every scene, alternating with
+    scan_layer.prepare_scans on the same scans; and, for context only, the numpy restatement of one scene on one host core. Per-launch kernel times come from a run of
+    this mode under a kernel trace (profiles/README.md), not from here."""
+    import time
+    import numpy as np
+    import torch
+    from epnet_amd import gt_aug_layer, scan_layer, synth
+    dev = torch.device("cuda:0")
+    p, n, e = 122880, 16384, 8192
+    objects = synth.gt_database(200, seed=9)
+    db = gt_aug_layer.GTDatabase.from_list(objects, dev)
+    cfg = gt_aug_layer.default_cfg()
+    base = [synth.lidar_scan(p - 1500 * k, seed=60 + k) for k in range(8)]
+    scenes = [int(v) for v in args.gt_aug_scenes.split(",")]
+    for bsz in scenes:
+        pts, num_raw = scan_layer.collate_scans([base[k % 8] for k in range(bsz)])
+        pts, num_raw = pts.to(dev), num_raw.to(dev)
+        cal = [synth.calibration(k % 8) for k in range(bsz)]
+        V2C, R0, P2, shape = (torch.stack([c[j] for c in cal]).to(dev) for j in range(4))
+        gts = torch.zeros((bsz, 20, 7))
+        for k in range(bsz):
+            gts[k, :12] = synth.object_boxes(12, 40 + k % 8)
+        gts, alpha = gts.to(dev), torch.zeros((bsz, 20), device=dev)
+        count = torch.full((bsz,), 12, dtype=torch.int32, device=dev)
+        plane = torch.tensor([[0.0, -1.0, 0.0, 1.65]] * bsz, dtype=torch.float64, device=dev)
+        tables = gt_aug_layer.draw_tables(bsz, p, db, e, n, cfg, torch.Generator(device=dev).manual_seed(11), dev)
+        tables["apply"] = torch.ones_like(tables["apply"])                 # every timed scene is augmented (GT_AUG_APPLY_PROB is not timed)
+        plain_tables = {"keys": tables["keys"][:, :p].contiguous(), "slot_perm": tables["slot_perm"]}
+
+        def fused():
+            return gt_aug_layer.prepare_scans_gt_aug(pts, num_raw, V2C, R0, P2, shape, tables, db, gts, count, gts, alpha, count, plane,
+                                                     npoints=n, extra_rows=e, cfg=cfg)
+
+        def plain():
+            return scan_layer.prepare_scans(pts, num_raw, V2C, R0, P2, shape, plain_tables, npoints=n)
+        got = fused()
+        info, scene_info = got["gt_aug_info"].cpu(), got["scene_info"].cpu()
+        ms_p, ms_f = timeit_pair(plain, fused)
+        row = {"scenes": bsz, "P": p, "E": e, "N": n, "objects": 200, "existing": 12, "launches": 6, "applied": int(info[:, 0].sum()),
+               "accepted": info[:4, 4].tolist(), "overlap_rejections": info[:4, 5].tolist(), "capacity_rejections": int(info[:, 6].sum()),
+               "extra_points": info[:4, 7].tolist(), "removed": scene_info[:4, 6].tolist()}
+        if args.gt_aug_side == "fused":                                   # what a kernel trace of the launches per call needs
+            for _ in range(args.reps):
+                fused()
+            torch.cuda.synchronize()
+        report("prepare_scans_gt_aug", row, ms_f, bsz * (p * 20 + e * 36 + n * 44),
+               "apply forced to 1 in every scene; placement + points + classify / plan / count / emit over P + E rows, no host sync; scan_layer.prepare_scans on the same "
+               "scans, alternating: %.4f ms" % ms_p)
+    if args.gt_aug_side == "fused":
+        return
+    # for context only: the restatement of ONE scene on one host core (numpy; the reference's own loop needs shapely and was not timed)
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tests"))
+    import gt_aug_restate as gr
+    host_db = gr.pack_database(objects)
+    one = {k: v[0].cpu().numpy() for k, v in tables.items()}
+    scene = dict(pts=pts[0].cpu().numpy(), num_raw=int(num_raw[0]), V2C=V2C[0].cpu().numpy(), R0=R0[0].cpu().numpy(), P2=P2[0].cpu().numpy(),
+                 img_shape=shape[0].cpu().numpy(), all_boxes=gts[0, :12].cpu().numpy(), gt_boxes=gts[0, :12].cpu().numpy(),
+                 gt_alpha=np.zeros(12, np.float32), plane=plane[0].cpu().numpy())
+    assert int(one["apply"]) == 1                                          # the device rows above ran this scene with the same tables
+    t0 = time.perf_counter()
+    placed = gr.place(host_db, 1, one["extra_num"], one["cand"], scene["all_boxes"], scene["gt_boxes"], scene["gt_alpha"], scene["plane"], e)
+    t1 = time.perf_counter()
+    extra = gr.object_points(host_db, placed, e)
+    out = gr.prepare_aug(scene["pts"], scene["num_raw"], scene["V2C"], scene["R0"], scene["P2"], scene["img_shape"], extra, placed["info"][7],
+                         placed["remove_boxes"], placed["info"][4], one["keys"], one["slot_perm"], n)
+    t2 = time.perf_counter()
+    print(json.dumps({"op": "prepare_scans_gt_aug/numpy_restatement", "shape": {"scenes": 1, "P": p, "E": e, "N": n, "accepted": int(placed["info"][4]),
+                                                                                "removed": int(out["scene_info"][6])},
+                      "ms": round((t2 - t0) * 1e3, 1), "reps": 1,
+                      "note": "one host core, one scene, for context only: the loop of tries %.1f ms (Python), points + removal + sampling %.1f ms "
+                              "(numpy)" % ((t1 - t0) * 1e3, (t2 - t1) * 1e3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--gt-aug-only", action="store_true",
+                    help="only GT-database augmentation: gt_aug_layer.prepare_scans_gt_aug against scan_layer.prepare_scans on the same scans")
+    ap.add_argument("--gt-aug-side", default="both", choices=["both", "fused"],
+                    help="with --gt-aug-only: fused = --reps more calls per size and no host restatement (for a kernel trace)")
+    ap.add_argument("--gt-aug-scenes", default="1,2,16,256", help="with --gt-aug-only: the batch sizes, comma separated")
     ap.add_argument("--loss-only", action="store_true", help="only the training-loss rows (fused against the two stock-torch forms)")
     ap.add_argument("--targets-only", action="store_true", help="only the RPN training targets (fused against bench_step.rpn_labels)")
     ap.add_argument("--scan-only", action="store_true",
@@ -901,6 +981,8 @@ def main():
         return rcnn_targets_rows(args, report, timeit_pair)
     if args.scan_only:
         return scan_rows(args, report, timeit_pair)
+    if args.gt_aug_only:
+        return gt_aug_rows(args, report, timeit_pair)
     if args.handover_only:
         return handover_rows(args, report, timeit_pair)
     if args.rows16_only:

@@ -307,6 +307,10 @@ def main():
                     help="where the step starts: from the (B,N,3) point arrays a loader would hand over (default), or, with --rpn-only, "
                          "from raw scans (synth.lidar_scan, 122 880 points each) through scan_layer.prepare_scans and "
                          "rpn_target_layer.augment_and_label on the device, fresh draws every step, no host synchronisation")
+    ap.add_argument("--gt-aug", action="store_true",
+                    help="with --inputs raw: GT-database augmentation of the point-only loader between the validity filter and the "
+                         "sampling (gt_aug_layer.prepare_scans_gt_aug on a synthetic database of 200 objects, fresh draws every step, "
+                         "no host synchronisation); a pasted object has no pixels, so the flag is refused together with --image")
     ap.add_argument("--amp", default="off", choices=["off", "bf16"],
                     help="bf16: forward under torch.autocast('cuda', torch.bfloat16) -- dense layers and this package's SA / FP operators on "
                          "bfloat16 rows, parameters and their gradients float32 (float16 is not offered: training in it needs loss "
@@ -319,6 +323,8 @@ def main():
     args = ap.parse_args()
     if args.two_stage and not args.infer:
         ap.error("--two-stage belongs to --infer")
+    if args.gt_aug and (args.image or args.inputs != "raw"):
+        ap.error("--gt-aug belongs to the point-only loader: --rpn-only --inputs raw, without --image")
     if args.inputs == "raw" and (not args.rpn_only or args.image or args.infer):
         ap.error("--inputs raw starts the point-stream RPN step (--rpn-only, without --image) from raw scans")
     if args.infer and args.image:
@@ -387,15 +393,28 @@ def main():
         cal = [synth.calibration(1000 * rank + k) for k in range(args.batch)]
         raw = {"scans": scans.to(device), "num_raw": num_raw.to(device), "cal": [torch.stack([c[j] for c in cal]).to(device) for j in range(4)],
                "alpha": torch.zeros(gts.shape[:2], device=device)}
+        if args.gt_aug:
+            from epnet_amd import gt_aug_layer
+            raw.update(db=gt_aug_layer.GTDatabase.from_list(synth.gt_database(200, seed=500 + rank), device), cfg=gt_aug_layer.default_cfg(),
+                       num_boxes=torch.full((args.batch,), 12, dtype=torch.int32, device=device),      # synthetic_batch fills 12 rows
+                       plane=torch.tensor([[0.0, -1.0, 0.0, 1.65]] * args.batch, dtype=torch.float64, device=device))
 
     def step_inputs():
         """--inputs raw: this step's points from the raw scans, sampled, shuffled and augmented on the device"""
         if raw is None:
             return xyz, gts
-        tables = scan_layer.draw_scan_tables(args.batch, raw["scans"].shape[1], args.points, None, device)
-        got = scan_layer.prepare_scans(raw["scans"], raw["num_raw"], *raw["cal"], tables, npoints=args.points)
+        step_gts, step_alpha = gts, raw["alpha"]
+        if args.gt_aug:
+            tables = gt_aug_layer.draw_tables(args.batch, raw["scans"].shape[1], raw["db"], 8192, args.points, raw["cfg"], None, device)
+            got = gt_aug_layer.prepare_scans_gt_aug(raw["scans"], raw["num_raw"], *raw["cal"], tables, raw["db"], gts, raw["num_boxes"], gts,
+                                                    raw["alpha"], raw["num_boxes"], raw["plane"], npoints=args.points, extra_rows=8192,
+                                                    cfg=raw["cfg"])
+            step_gts, step_alpha = got["gt_boxes3d"], got["gt_alpha"]
+        else:
+            tables = scan_layer.draw_scan_tables(args.batch, raw["scans"].shape[1], args.points, None, device)
+            got = scan_layer.prepare_scans(raw["scans"], raw["num_raw"], *raw["cal"], tables, npoints=args.points)
         aug = rpn_target_layer.draw_augmentation(args.batch, device=device)
-        pts, boxes, cls_label, reg_label = rpn_target_layer.augment_and_label(got["pts_rect"], gts, raw["alpha"], aug)
+        pts, boxes, cls_label, reg_label = rpn_target_layer.augment_and_label(got["pts_rect"], step_gts, step_alpha, aug)
         if args.loss != "placeholder":                     # the labels of THIS step's points
             (model.module if hasattr(model, "module") else model).rpn_labels = (cls_label, reg_label)
         return pts, boxes
@@ -530,6 +549,7 @@ def main():
                           "per_rank_ms_per_step": {"min": min(r_["ms_per_step"] for r_ in per_rank),
                                                    "max": max(r_["ms_per_step"] for r_ in per_rank)},
                           "loss": last, "data": "synthetic", "dtype": "f32" if args.amp == "off" else "bf16 autocast (parameters f32)", **({} if raw is None else {"inputs": "raw"}),
+                          **({} if not args.gt_aug else {"gt_aug": True}),
                           **({} if args.optimizer == "sgd" else {"optimizer": args.optimizer}),
                           **({} if args.optimizer != "fused" else {"optimizer_stats": dict(zip(optim.optim_cuda.STATS_NAMES, opt.stats.tolist()))}),
                           **({} if args.loss == "placeholder" else {"loss_mode": args.loss, "loss_terms": {

@@ -120,6 +120,12 @@ SIGNATURES = {
     "epnet_scan_prepare_workspace_bytes": (_sz, [_i, _i, _i]),
     "epnet_scan_prepare": (_i, [_i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_image_normalise": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_gt_aug_place": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_gt_aug_points": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "epnet_scan_prepare_aug_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "epnet_scan_prepare_aug": (_i, [_i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_kitti_overlaps": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_kitti_match": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_kitti_pr_workspace_bytes": (_sz, [_i, _i, _i]),

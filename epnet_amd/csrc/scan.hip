@@ -47,13 +47,13 @@ struct Layout {
     size_t valid, near, tile_cnt, plan, tile_sel, total;
 };
 
-__host__ __device__ inline Layout layout(int b, int tiles) {
+__host__ __device__ inline Layout layout(int b, int tiles, int cnt_ints = 2) {
     Layout l;
     const size_t words = (size_t)b * (size_t)tiles * kWords;
     l.valid = 0;
     l.near = l.valid + words * 8;
     l.tile_cnt = l.near + words * 8;
-    l.plan = l.tile_cnt + (size_t)b * tiles * 2 * sizeof(int);
+    l.plan = l.tile_cnt + (size_t)b * tiles * cnt_ints * sizeof(int);
     l.tile_sel = l.plan + (size_t)b * kPlanInts * sizeof(int);
     l.total = l.tile_sel + (size_t)b * tiles * 2 * sizeof(int);
     return l;
@@ -111,32 +111,113 @@ __device__ __forceinline__ int set_count(int set, int v, int f) {
     return set == kValid ? v : (set == kNear ? v - f : (set == kFar ? f : 0));
 }
 
+// ---- the variant with ground-truth database objects (epnet_scan_prepare_aug): the index space is the p raw rows, then e rows of
+// pasted objects that are rectified already; a raw row inside one of the scene's removal boxes is not valid. AUG is a
+// compile-time switch of the four kernels: with AUG == false they are the kernels of epnet_scan_prepare as they were, down to
+// their arguments -- the AugArgs travel in a parameter pack that is empty then.
+constexpr int kMaxRemove = 32;                     // EPNET_GT_AUG_MAX_ACCEPT
+
+struct AugArgs {
+    int p_raw, e, k_max, count_stride;             // num_remove[k * count_stride], num_extra[k * count_stride]
+    const f4 *extra;                               // (b,e,4) [x, y, z, intensity], rectified
+    const int *num_extra;
+    const float *remove_boxes;                     // (b,k_max,7)
+    const int *num_remove;
+};
+
+struct NoArgs {};
+
+__device__ __forceinline__ NoArgs first_arg() { return NoArgs(); }
+__device__ __forceinline__ const AugArgs &first_arg(const AugArgs &a) { return a; }
+
+__device__ __forceinline__ int clamp_count(const int *__restrict__ counts, int at, int cap) {
+    const int r = counts[at];
+    return r < 0 ? 0 : (r > cap ? cap : r);
+}
+
+// the pixel of a rectified point: the second half of transform()
+__device__ __forceinline__ Point project(const Calib &c, const f4 row) {
+    Point q;
+    q.x = row.x; q.y = row.y; q.z = row.z;
+    const float p0 = ((q.x * c.p[0][0] + q.y * c.p[0][1]) + q.z * c.p[0][2]) + c.p[0][3];
+    const float p1 = ((q.x * c.p[1][0] + q.y * c.p[1][1]) + q.z * c.p[1][2]) + c.p[1][3];
+    const float p2 = ((q.x * c.p[2][0] + q.y * c.p[2][1]) + q.z * c.p[2][2]) + c.p[2][3];
+    q.u = p0 / q.z;
+    q.v = p1 / q.z;
+    q.depth = p2 - c.p[2][3];
+    return q;
+}
+
+// pt_in_box3d (roipool3d_kernel.cu:14-28) as roipool3d.hip evaluates it; s = [cx, cy, cz, hh, hw, hl, cosa, sina]
+__device__ __forceinline__ void remove_box_setup(const float *__restrict__ bx, float *s) {
+    const float h = bx[3];
+    s[0] = bx[0]; s[1] = (float)((double)bx[1] - (double)h / 2.0); s[2] = bx[2];
+    s[3] = h * 0.5f; s[4] = bx[4] * 0.5f; s[5] = bx[5] * 0.5f;
+    s[6] = (float)cos((double)bx[6]); s[7] = (float)sin((double)bx[6]);
+}
+
+__device__ __forceinline__ bool in_remove_box(const float *s, float x, float y, float z) {
+    const float max_dis = 10.0f;
+    if ((fabsf(x - s[0]) > max_dis) || (fabsf(y - s[1]) > s[3]) || (fabsf(z - s[2]) > max_dis)) return false;
+    const float nsina = -s[7];
+    const float x_rot = (x - s[0]) * s[6] + (z - s[2]) * nsina;
+    const float z_rot = (x - s[0]) * s[7] + (z - s[2]) * s[6];
+    return (x_rot >= -s[5]) & (x_rot <= s[5]) & (z_rot >= -s[4]) & (z_rot <= s[4]);
+}
+
 // ---- 1. classify: grid (tiles, b)
+template <bool AUG, typename... Aug>
 __global__ __launch_bounds__(kThreads) void scan_classify_kernel(int p, int reduce_by_range, Scope scope, float near_depth,
                                                                  const f4 *__restrict__ pts, const int *__restrict__ num_raw,
                                                                  const float *__restrict__ V2C, const float *__restrict__ R0,
                                                                  const float *__restrict__ P2, const int *__restrict__ img_shape,
                                                                  u64 *__restrict__ ws_valid, u64 *__restrict__ ws_near,
-                                                                 int *__restrict__ ws_tile_cnt) {
-    __shared__ int s_cnt[kWaves][2];
+                                                                 int *__restrict__ ws_tile_cnt, Aug... aug_pack) {
+    const auto aug = first_arg(aug_pack...);
+    constexpr int kC = AUG ? 3 : 2;                // counts per tile: valid, far and, AUG, removed
+    __shared__ int s_cnt[kWaves][kC];
+    __shared__ float s_box[AUG ? kMaxRemove : 1][8];
     int wg_x, bs;
     xcd_scene_map(wg_x, bs);
     const int tiles = (int)gridDim.x, t = threadIdx.x, wave = t >> 6;
     const Calib c = load_calib(V2C, R0, P2, img_shape, bs);
-    const int raw = clamp_raw(num_raw, bs, p);
-    const f4 *rows = pts + (size_t)bs * (size_t)p;
+    int p_raw = p, n_extra = 0, n_remove = 0;      // AUG: p is the size of the index space, p_raw the raw rows of a scene
+    const f4 *extra = nullptr;
+    if constexpr (AUG) {
+        p_raw = aug.p_raw;
+        n_extra = aug.e > 0 ? clamp_count(aug.num_extra, bs * aug.count_stride, aug.e) : 0;
+        n_remove = aug.k_max > 0 ? clamp_count(aug.num_remove, bs * aug.count_stride, aug.k_max) : 0;
+        extra = aug.extra + (size_t)bs * (size_t)aug.e;
+        if (t < n_remove) remove_box_setup(aug.remove_boxes + ((size_t)bs * aug.k_max + t) * 7, s_box[t]);
+        __syncthreads();
+    }
+    const int raw = clamp_raw(num_raw, bs, p_raw);
+    const f4 *rows = pts + (size_t)bs * (size_t)p_raw;
     const size_t word0 = ((size_t)bs * tiles + wg_x) * kWords;
-    int cnt_v = 0, cnt_f = 0;
+    int cnt_v = 0, cnt_f = 0, cnt_r = 0;
 #pragma unroll
     for (int it = 0; it < kIters; ++it) {
         const int i = wg_x * kTile + it * kThreads + t;
-        const f4 row = rows[i < p ? i : p - 1];                 // clamped: no load under a condition
+        const f4 row = rows[i < p_raw ? i : p_raw - 1];         // clamped: no load under a condition
         const Point q = transform(c, row);
         bool ok = i < raw && q.u >= 0.f && q.u < c.w && q.v >= 0.f && q.v < c.h && q.depth >= 0.f;
         if (reduce_by_range)
             ok = ok && (double)q.x >= scope.v[0] && (double)q.x <= scope.v[1] && (double)q.y >= scope.v[2] &&
                  (double)q.y <= scope.v[3] && (double)q.z >= scope.v[4] && (double)q.z <= scope.v[5];
-        const u64 vb = __ballot(ok), nb = __ballot(ok && q.z < near_depth);
+        float z = q.z;
+        if constexpr (AUG) {
+            bool removed = false;
+            if (ok)
+                for (int k = 0; k < n_remove; ++k) removed = removed || in_remove_box(s_box[k], q.x, q.y, q.z);
+            cnt_r += __popcll(__ballot(ok && removed));
+            ok = ok && !removed;
+            const int j = i - p_raw;                            // the extra row, when not negative
+            if (aug.e > 0) {                                    // uniform
+                const f4 xr = extra[j >= 0 && j < aug.e ? j : 0];
+                if (j >= 0) { ok = j < n_extra; z = xr.z; }
+            }
+        }
+        const u64 vb = __ballot(ok), nb = __ballot(ok && z < near_depth);
         if ((t & 63) == 0) {
             ws_valid[word0 + it * kWaves + wave] = vb;
             ws_near[word0 + it * kWaves + wave] = nb;
@@ -144,36 +225,49 @@ __global__ __launch_bounds__(kThreads) void scan_classify_kernel(int p, int redu
         cnt_v += __popcll(vb);
         cnt_f += __popcll(vb & ~nb);
     }
-    if ((t & 63) == 0) { s_cnt[wave][0] = cnt_v; s_cnt[wave][1] = cnt_f; }
+    if ((t & 63) == 0) {
+        s_cnt[wave][0] = cnt_v; s_cnt[wave][1] = cnt_f;
+        if constexpr (AUG) s_cnt[wave][2] = cnt_r;
+    }
     __syncthreads();
     if (t == 0) {
-        int v = 0, f = 0;
+        int v = 0, f = 0, r = 0;
 #pragma unroll
-        for (int k = 0; k < kWaves; ++k) { v += s_cnt[k][0]; f += s_cnt[k][1]; }
-        ws_tile_cnt[((size_t)bs * tiles + wg_x) * 2] = v;
-        ws_tile_cnt[((size_t)bs * tiles + wg_x) * 2 + 1] = f;
+        for (int k = 0; k < kWaves; ++k) {
+            v += s_cnt[k][0]; f += s_cnt[k][1];
+            if constexpr (AUG) r += s_cnt[k][2];
+        }
+        ws_tile_cnt[((size_t)bs * tiles + wg_x) * kC] = v;
+        ws_tile_cnt[((size_t)bs * tiles + wg_x) * kC + 1] = f;
+        if constexpr (AUG) ws_tile_cnt[((size_t)bs * tiles + wg_x) * kC + 2] = r;
     }
 }
 
 // ---- 2. plan: grid (b), one workgroup per scene
+template <bool AUG, typename... Aug>
 __global__ __launch_bounds__(kPlanThreads) void scan_plan_kernel(int p, int n, int tiles, const int *__restrict__ num_raw,
                                                                  const unsigned *__restrict__ keys, const u64 *__restrict__ ws_valid,
                                                                  const u64 *__restrict__ ws_near, const int *__restrict__ ws_tile_cnt,
-                                                                 int *__restrict__ ws_plan, int *__restrict__ scene_info) {
+                                                                 int *__restrict__ ws_plan, int *__restrict__ scene_info, Aug... aug_pack) {
+    const auto aug = first_arg(aug_pack...);
+    constexpr int kC = AUG ? 3 : 2;
     __shared__ int s_hist[256];
-    __shared__ int s_sum[2];
+    __shared__ int s_sum[kC];
     __shared__ int s_pick[2];                      // the bin that holds the rem-th key, and the keys below that bin
     const int bs = blockIdx.x, t = threadIdx.x;
-    if (t < 2) s_sum[t] = 0;
+    if (t < kC) s_sum[t] = 0;
     __syncthreads();
     {
-        int v = 0, f = 0;
+        int v = 0, f = 0, removed = 0;
         for (int k = t; k < tiles; k += kPlanThreads) {
-            v += ws_tile_cnt[((size_t)bs * tiles + k) * 2];
-            f += ws_tile_cnt[((size_t)bs * tiles + k) * 2 + 1];
+            v += ws_tile_cnt[((size_t)bs * tiles + k) * kC];
+            f += ws_tile_cnt[((size_t)bs * tiles + k) * kC + 1];
+            if constexpr (AUG) removed += ws_tile_cnt[((size_t)bs * tiles + k) * kC + 2];
         }
         if (v) atomicAdd(&s_sum[0], v);
         if (f) atomicAdd(&s_sum[1], f);
+        if constexpr (AUG)
+            if (removed) atomicAdd(&s_sum[2], removed);
     }
     __syncthreads();
     const int V = s_sum[0], F = s_sum[1];
@@ -232,8 +326,15 @@ __global__ __launch_bounds__(kPlanThreads) void scan_plan_kernel(int p, int n, i
         int *pl = ws_plan + (size_t)bs * kPlanInts;
         pl[0] = kase; pl[1] = q; pl[2] = r; pl[3] = (int)prefix; pl[4] = r > 0 ? rem : 0; pl[5] = cand; pl[6] = forced;
         pl[7] = set_count(forced, V, F);
-        int *si = scene_info + (size_t)bs * 6;
-        si[0] = clamp_raw(num_raw, bs, p); si[1] = V; si[2] = F; si[3] = kase; si[4] = r; si[5] = q;
+        if constexpr (AUG) {
+            int *si = scene_info + (size_t)bs * 8;
+            si[0] = clamp_raw(num_raw, bs, aug.p_raw); si[1] = V; si[2] = F; si[3] = kase; si[4] = r; si[5] = q;
+            si[6] = s_sum[2];
+            si[7] = aug.e > 0 ? clamp_count(aug.num_extra, bs * aug.count_stride, aug.e) : 0;
+        } else {
+            int *si = scene_info + (size_t)bs * 6;
+            si[0] = clamp_raw(num_raw, bs, p); si[1] = V; si[2] = F; si[3] = kase; si[4] = r; si[5] = q;
+        }
     }
 }
 
@@ -291,13 +392,16 @@ __device__ __forceinline__ void put_row(const Outputs &o, const int *__restrict_
 }
 
 // ---- 4. emit: grid (tiles, b)
+template <bool AUG, typename... Aug>
 __global__ __launch_bounds__(kThreads) void scan_emit_kernel(int p, int n, const f4 *__restrict__ pts, const float *__restrict__ V2C,
                                                              const float *__restrict__ R0, const float *__restrict__ P2,
                                                              const int *__restrict__ img_shape, const unsigned *__restrict__ keys,
                                                              const int *__restrict__ slot_perm, const u64 *__restrict__ ws_valid,
                                                              const u64 *__restrict__ ws_near, const int *__restrict__ ws_tile_cnt,
                                                              const int *__restrict__ ws_plan, const int *__restrict__ ws_tile_sel,
-                                                             Outputs o) {
+                                                             Outputs o, Aug... aug_pack) {
+    const auto aug = first_arg(aug_pack...);
+    constexpr int kC = AUG ? 3 : 2;
     __shared__ int s_before[3];                    // forced, below the threshold, at the threshold: in the tiles before this one
     __shared__ u64 s_mask[3][kWords];
     __shared__ int s_pre[3][kWords];               // the same three counts in the words of this tile before word j
@@ -324,8 +428,8 @@ __global__ __launch_bounds__(kThreads) void scan_emit_kernel(int p, int n, const
     {
         int a = 0, l = 0, e = 0;
         for (int k = t; k < wg_x; k += kThreads) {
-            const size_t at = ((size_t)bs * tiles + k) * 2;
-            a += set_count(forced, ws_tile_cnt[at], ws_tile_cnt[at + 1]);
+            const size_t at = ((size_t)bs * tiles + k) * 2, at_cnt = ((size_t)bs * tiles + k) * kC;
+            a += set_count(forced, ws_tile_cnt[at_cnt], ws_tile_cnt[at_cnt + 1]);
             l += ws_tile_sel[at];
             e += ws_tile_sel[at + 1];
         }
@@ -358,7 +462,9 @@ __global__ __launch_bounds__(kThreads) void scan_emit_kernel(int p, int n, const
     }
     __syncthreads();
     const Calib c = load_calib(V2C, R0, P2, img_shape, bs);
-    const f4 *rows = pts + (size_t)bs * (size_t)p;
+    int p_raw = p;
+    if constexpr (AUG) p_raw = aug.p_raw;
+    const f4 *rows = pts + (size_t)bs * (size_t)p_raw;
     // who is chosen, and the ballots of it, in a loop of their own: every ballot is taken with the whole wave active, before
     // the write loop below diverges
     bool chosen_it[kIters];
@@ -377,8 +483,15 @@ __global__ __launch_bounds__(kThreads) void scan_emit_kernel(int p, int n, const
         const bool chosen = chosen_it[it];
         const u64 cb = chosen_mask[it];
         if (!(in_forced[it] || chosen)) continue;
-        const f4 row = rows[i];                                   // a set bit is a row below num_raw <= p
-        const Point pt = transform(c, row);
+        f4 row;
+        Point pt;
+        if (!AUG || i < p_raw) {
+            row = rows[i];                                        // a set bit is a row below num_raw <= p
+            pt = transform(c, row);
+        } else if constexpr (AUG) {
+            row = aug.extra[(size_t)bs * (size_t)aug.e + (size_t)(i - p_raw)];   // a set bit is a row below num_extra <= e
+            pt = project(c, row);
+        }
         const float intensity = row.w - 0.5f;
         if (in_forced[it]) {
             const int rank = s_before[0] + s_pre[0][j] + popc_below(s_mask[0][j]);
@@ -471,15 +584,65 @@ extern "C" int epnet_scan_prepare(int b, int p, int n, int reduce_by_range, cons
     const unsigned *ukeys = (const unsigned *)keys;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)tiles, (unsigned)b), block(scan::kThreads);
-    hipLaunchKernelGGL(scan::scan_classify_kernel, grid, block, 0, st, p, reduce_by_range, sc, near_depth, rows, num_raw, V2C, R0, P2,
+    hipLaunchKernelGGL(scan::scan_classify_kernel<false>, grid, block, 0, st, p, reduce_by_range, sc, near_depth, rows, num_raw, V2C, R0, P2,
                        img_shape, ws_valid, ws_near, ws_tile_cnt);
-    hipLaunchKernelGGL(scan::scan_plan_kernel, dim3((unsigned)b), dim3(scan::kPlanThreads), 0, st, p, n, tiles, num_raw, ukeys, ws_valid,
-                       ws_near, ws_tile_cnt, ws_plan, scene_info);
+    hipLaunchKernelGGL(scan::scan_plan_kernel<false>, dim3((unsigned)b), dim3(scan::kPlanThreads), 0, st, p, n, tiles, num_raw, ukeys,
+                       ws_valid, ws_near, ws_tile_cnt, ws_plan, scene_info);
     hipLaunchKernelGGL(scan::scan_count_kernel, grid, block, 0, st, p, ukeys, ws_valid, ws_near, ws_plan, ws_tile_sel);
     const scan::Outputs o = {pts_rect, pts_intensity, pts_origin_xy, pts_input, choice};
-    hipLaunchKernelGGL(scan::scan_emit_kernel, grid, block, 0, st, p, n, rows, V2C, R0, P2, img_shape, ukeys, slot_perm, ws_valid, ws_near,
-                       ws_tile_cnt, ws_plan, ws_tile_sel, o);
+    hipLaunchKernelGGL(scan::scan_emit_kernel<false>, grid, block, 0, st, p, n, rows, V2C, R0, P2, img_shape, ukeys, slot_perm, ws_valid,
+                       ws_near, ws_tile_cnt, ws_plan, ws_tile_sel, o);
     return check_launch("scan_prepare");
+}
+
+static bool scan_aug_limits(int b, int p, int e, int n, int k_max) {
+    return scan_limits(b, p, n) && e >= 0 && e <= 1048576 && p + e <= 1048576 && k_max >= 0 && k_max <= scan::kMaxRemove;
+}
+
+extern "C" size_t epnet_scan_prepare_aug_workspace_bytes(int b, int p, int e, int n) {
+    if (b <= 0 || !scan_aug_limits(b, p, e, n, 0)) return 0;
+    return scan::layout(b, div_up(p + e, scan::kTile), 3).total;
+}
+
+extern "C" int epnet_scan_prepare_aug(int b, int p, int e, int n, int k_max, int reduce_by_range, const double *scope, float near_depth,
+                                      const float *pts_lidar, const int *num_raw, const float *V2C, const float *R0, const float *P2,
+                                      const int *img_shape, const float *extra_pts, const int *num_extra, const float *remove_boxes,
+                                      const int *num_remove, int count_stride, const int *keys, const int *slot_perm, void *workspace,
+                                      size_t workspace_bytes, float *pts_rect, float *pts_intensity, float *pts_origin_xy,
+                                      float *pts_input, int *choice, int *scene_info, epnet_stream_t stream) {
+    EPNET_REQUIRE(b >= 0);
+    if (b == 0) return EPNET_OK;
+    if (!scan_aug_limits(b, p, e, n, k_max)) return EPNET_ELIMIT;
+    EPNET_REQUIRE(pts_lidar && num_raw && V2C && R0 && P2 && img_shape && keys && workspace);
+    EPNET_REQUIRE(pts_rect && pts_intensity && pts_origin_xy && choice && scene_info);
+    EPNET_REQUIRE(scope || !reduce_by_range);
+    EPNET_REQUIRE(count_stride >= 1 && (e == 0 || (extra_pts && num_extra)) && (k_max == 0 || (remove_boxes && num_remove)));
+    EPNET_REQUIRE(((uintptr_t)pts_lidar & 15) == 0 && ((uintptr_t)extra_pts & 15) == 0 && ((uintptr_t)workspace & 7) == 0);
+    const int total = p + e, tiles = div_up(total, scan::kTile);
+    const scan::Layout l = scan::layout(b, tiles, 3);
+    if (workspace_bytes < l.total) return EPNET_ENOMEM;
+    scan::Scope sc;
+    for (int k = 0; k < 6; ++k) sc.v[k] = scope ? scope[k] : 0.0;
+    char *ws = (char *)workspace;
+    scan::u64 *ws_valid = (scan::u64 *)(ws + l.valid), *ws_near = (scan::u64 *)(ws + l.near);
+    int *ws_tile_cnt = (int *)(ws + l.tile_cnt), *ws_plan = (int *)(ws + l.plan), *ws_tile_sel = (int *)(ws + l.tile_sel);
+    const scan::f4 *rows = (const scan::f4 *)pts_lidar;
+    const unsigned *ukeys = (const unsigned *)keys;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)tiles, (unsigned)b), block(scan::kThreads);
+    scan::AugArgs aug;
+    aug.p_raw = p; aug.e = e; aug.k_max = k_max; aug.count_stride = count_stride;
+    aug.extra = (const scan::f4 *)extra_pts; aug.num_extra = num_extra; aug.remove_boxes = remove_boxes; aug.num_remove = num_remove;
+    // the kernels' `p` is the size of the index space: raw rows, then extra rows
+    hipLaunchKernelGGL(scan::scan_classify_kernel<true>, grid, block, 0, st, total, reduce_by_range, sc, near_depth, rows, num_raw, V2C, R0,
+                       P2, img_shape, ws_valid, ws_near, ws_tile_cnt, aug);
+    hipLaunchKernelGGL(scan::scan_plan_kernel<true>, dim3((unsigned)b), dim3(scan::kPlanThreads), 0, st, total, n, tiles, num_raw, ukeys,
+                       ws_valid, ws_near, ws_tile_cnt, ws_plan, scene_info, aug);
+    hipLaunchKernelGGL(scan::scan_count_kernel, grid, block, 0, st, total, ukeys, ws_valid, ws_near, ws_plan, ws_tile_sel);
+    const scan::Outputs o = {pts_rect, pts_intensity, pts_origin_xy, pts_input, choice};
+    hipLaunchKernelGGL(scan::scan_emit_kernel<true>, grid, block, 0, st, total, n, rows, V2C, R0, P2, img_shape, ukeys, slot_perm, ws_valid,
+                       ws_near, ws_tile_cnt, ws_plan, ws_tile_sel, o, aug);
+    return check_launch("scan_prepare_aug");
 }
 
 extern "C" int epnet_image_normalise(int b, int h_in, int w_in, int h_out, int w_out, const uint8_t *img, const int *img_shape,

@@ -128,6 +128,26 @@ def lidar_scan(p, seed=0):
     return torch.cat([xyz, u[:, 4:5]], dim=1).contiguous()
 
 
+def gt_database(num, seed=0, min_points=3, max_points=600):
+    """a GT database in the form tools/generate_gt_database.py pickles: a list of `num` dicts with 'gt_box3d' (7) float32 (car-sized,
+    anywhere object_boxes puts them), 'points' (n,3) on the box's surfaces, 'intensity' (n) in [0, 1) and 'alpha'; n is
+    log-uniform on [min_points, max_points], so that both the easy (more than 100 points) and the hard list are populated"""
+    g = _gen(seed + 86028121)
+    boxes = object_boxes(num, seed + 1)
+    out = []
+    for k in range(num):
+        u = torch.rand((3,), generator=g, dtype=torch.float32)
+        n = int(min_points * (max_points / float(min_points)) ** float(u[0]))
+        r = torch.rand((n, 4), generator=g, dtype=torch.float32)
+        h, w, l, ry = (float(v) for v in boxes[k, 3:7])
+        local = torch.stack([(r[:, 0] - 0.5) * l, -r[:, 1] * h, (r[:, 2] - 0.5) * w], dim=1)
+        c, s = math.cos(ry), math.sin(ry)
+        pts = torch.stack([local[:, 0] * c + local[:, 2] * s, local[:, 1], -local[:, 0] * s + local[:, 2] * c], dim=1) + boxes[k, :3]
+        out.append({"gt_box3d": boxes[k].numpy().copy(), "points": pts.contiguous().numpy(), "intensity": r[:, 3].contiguous().numpy(),
+                    "alpha": float((u[1] * 2 - 1) * math.pi)})
+    return out
+
+
 def calibration(seed=0):
     """KITTI-typical calibration: V2C (3,4), R0 (3,3), P2 (3,4) fp32 and img_shape int32 [h, w] = [375, 1242]; the seed moves
     the principal point and the mounting by amounts of the size that differ between recording days"""

@@ -778,6 +778,76 @@ int epnet_scan_prepare(int b, int p, int n, int reduce_by_range, const double *s
 int epnet_image_normalise(int b, int h_in, int w_in, int h_out, int w_out, const uint8_t *img, const int *img_shape,
                           const double *mean, const double *std, float *out, epnet_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------
+ * GT-database augmentation of the point-only loader (lib/datasets/kitti_rcnn_dataset.py:590-696, apply_gt_aug_to_one_scene,
+ * called from get_rpn_sample :443-455, :506-509; the box geometry of lib/utils/kitti_utils.py:66-103 and :198-238)
+ * -------------------------------------------------------------------------------------- */
+#define EPNET_GT_AUG_MAX_TRIES 128     /* tries per scene (the reference uses 100) */
+#define EPNET_GT_AUG_MAX_EXISTING 224  /* rows of all_gt_boxes3d per scene */
+#define EPNET_GT_AUG_MAX_ACCEPT 32     /* accepted objects per scene (k_max) */
+
+/* The reference's placement loop for b scenes in one launch (one wave per scene), the random decisions given as device tables.
+ * The database: db_boxes (D,7) f32 [x, y, z, h, w, l, ry], db_alpha (D) f32, db_npts (D) i32. Tables: apply (b) i32, extra_num
+ * (b) i32 (used as min(extra_num, k_max - 1); extra_max is the caller's bound on it and must be below k_max), cand (b,T) i32
+ * the database row of each try. The scene: all_boxes (b,a,7) with num_all (b) rows (every labelled object, for the overlap
+ * test), gt_boxes (b,g,7) / gt_alpha (b,g) with num_gt (b) rows (the label rows), road_plane (b,4) f64 [a, b, c, d]; counts
+ * are clamped to their capacity. scope as for epnet_scan_prepare. Per scene with apply != 0, tries t = 0..T-1 in order:
+ *   1. stop when cnt > extra_num;
+ *   2. with reduce_by_range, skip the candidate when its centre (x, y, z) is outside scope (compared in double, both ends
+ *      inclusive); a row outside [0, D) is skipped likewise;
+ *   3. skip it when db_npts < 5;
+ *   4. cur_height = ((-d - a * (double)x) - c * (double)z) / b; move = (double)y - cur_height; y' = (float)((double)y - move);
+ *   5. cnt += 1;
+ *   6. reject it (info[5]) when it overlaps a current box: the scene's all_boxes rows with w + 0.5f, l + 0.5f, then the
+ *      accepted candidates in the same form. Two boxes overlap when their vertical intervals [y - h, y] share a positive length
+ *      and overlap3d / union3d >= 1e-8, all in double on the float32 box values: the BEV rectangle has the corners
+ *      (x + dx cos ry + dz sin ry, z - dx sin ry + dz cos ry), dx = +-l/2, dz = +-w/2; overlap3d = shared area * shared
+ *      height, union3d = area_a * h_a + area_b * h_b - overlap3d (get_iou3d). A box with w or l of 0 shares no area. With no
+ *      current box the candidate is accepted;
+ *   7. reject it (info[6]) when k_max objects are accepted or its points do not fit in what is left of e rows;
+ *   8. else accept: [x, y', z, h, w + 0.5f, l + 0.5f, ry] joins the current boxes, [x, y', z, h + 2.0f, w, l, ry] is its
+ *      removal box, [x, y', z, h, w, l, ry] with db_alpha its label row, and its points take rows row0 .. row0 + npts of the
+ *      scene's extra rows, row0 the points accepted before it.
+ * The reference lowers the database object itself (obj.pos, :656), so a second use in one worker drifts; here the label is
+ * always the placed box. Outputs, every element written: acc_db (b,k_max) i32 the database row, -1 behind the count; acc_box
+ * (b,k_max,7), acc_move (b,k_max) f64, acc_row0 (b,k_max) i32, remove_boxes (b,k_max,7), zeros behind; gt_out (b,g+k_max,7)
+ * and alpha_out (b,g+k_max): the num_gt label rows, the accepted boxes directly behind them, zeros behind; info (b,8) i32 =
+ * [applied, extra_num, tries used, cnt, accepted, overlap rejections, capacity rejections, extra points]. T <=
+ * EPNET_GT_AUG_MAX_TRIES, a <= EPNET_GT_AUG_MAX_EXISTING, 1 <= k_max <= EPNET_GT_AUG_MAX_ACCEPT, extra_max < k_max,
+ * e <= 1048576, D >= 1, b <= 65535, else EPNET_ELIMIT before the launch; b == 0 returns EPNET_OK. */
+int epnet_gt_aug_place(int b, int T, int a, int g, int k_max, int e, int D, int extra_max, int reduce_by_range,
+                       const double *scope, const float *db_boxes, const float *db_alpha, const int *db_npts,
+                       const int *apply, const int *extra_num, const int *cand, const float *all_boxes, const int *num_all,
+                       const float *gt_boxes, const float *gt_alpha, const int *num_gt, const double *road_plane,
+                       int *acc_db, float *acc_box, double *acc_move, int *acc_row0, float *remove_boxes, float *gt_out,
+                       float *alpha_out, int *info, epnet_stream_t stream);
+
+/* The accepted objects' points in one launch: db_points (S,4) f32 [x, y, z, intensity] packed, object d at rows db_offsets[d]
+ * .. db_offsets[d+1] (db_offsets (D+1) i32); acc_db, acc_move, acc_row0, info as epnet_gt_aug_place wrote them. extra_pts
+ * (b,e,4): row acc_row0[k] + i of scene s is point i of its k-th accepted object with y = (float)((double)y - acc_move[k]);
+ * rows at or beyond info[7] are zero. Every element is written. 16-byte row loads and stores when db_points and extra_pts are
+ * 16-byte aligned, scalar ones otherwise. e == 0 or b == 0 returns EPNET_OK. */
+int epnet_gt_aug_points(int b, int e, int k_max, int D, int S, const float *db_points, const int *db_offsets,
+                        const int *acc_db, const double *acc_move, const int *acc_row0, const int *info, float *extra_pts,
+                        epnet_stream_t stream);
+
+/* epnet_scan_prepare over the index space [0, p) raw rows then [p, p + e) extra rows; keys is (b,p+e). A raw row is valid by
+ * epnet_scan_prepare's rule AND outside every one of the scene's num_remove[k * count_stride] removal boxes (remove_boxes
+ * (b,k_max,7), clamped to k_max <= EPNET_GT_AUG_MAX_ACCEPT); the membership test is pt_in_box3d's as epnet_roipool3d
+ * evaluates it (fp32, the 10 m gate included). An extra row (extra_pts (b,e,4) [x, y, z, intensity], rectified already,
+ * 16-byte aligned) below num_extra[k * count_stride] (clamped to e) is always valid, near or far by its z; its pts_origin_xy is
+ * the projection of the rectified point, its intensity column is lowered by 0.5f like a raw row's. count_stride >= 1 lets
+ * both counts be read from columns 4 and 7 of epnet_gt_aug_place's info. choice >= p names extra row choice - p. scene_info
+ * (b,8) i32 = [num_raw clamped, V, F, case, r, q, raw points removed, extra rows]. Four launches. With e == 0 and no removal
+ * box the outputs are epnet_scan_prepare's bits. p + e <= 1048576, else as epnet_scan_prepare. */
+size_t epnet_scan_prepare_aug_workspace_bytes(int b, int p, int e, int n);
+int epnet_scan_prepare_aug(int b, int p, int e, int n, int k_max, int reduce_by_range, const double *scope, float near_depth,
+                           const float *pts_lidar, const int *num_raw, const float *V2C, const float *R0, const float *P2,
+                           const int *img_shape, const float *extra_pts, const int *num_extra, const float *remove_boxes,
+                           const int *num_remove, int count_stride, const int *keys, const int *slot_perm, void *workspace,
+                           size_t workspace_bytes, float *pts_rect, float *pts_intensity, float *pts_origin_xy,
+                           float *pts_input, int *choice, int *scene_info, epnet_stream_t stream);
+
 /* ---- The KITTI AP evaluator (tools/kitti_object_eval_python: rotate_iou.py:18-296, a numba.cuda kernel, and eval.py:84-332,
  * numba CPU JIT). All frames of a call are ragged: frame f owns rows *_off[f] .. *_off[f+1] of the arrays that go with the
  * offset array (F+1 int32 each) and the dt_num[f] x gt_num[f] float64 block at ov_off[f] (F+1 int64), detection-major as
