@@ -354,6 +354,86 @@ def optim_rows(args, report):
            % statistics.median(tf))
 
 
+def optim_scaled_rows(args, report):
+    """the optimiser step with dynamic loss scaling on the same parameter list: FusedAdamOneCycle(loss_scale="dynamic") (three
+    launches) against its stock composition -- what torch.amp.GradScaler runs around today's fused step, WITHOUT the host read of
+    found_inf that GradScaler.step adds (so the comparator is sync-free too): found_inf and 1 / scale as GradScaler makes them,
+    torch._amp_foreach_non_finite_check_and_unscale_, FusedAdamOneCycle.step(), torch._amp_update_scale_. ALTERNATING inside one
+    call, the median of --reps per side, two passes; the gradients (finite, 65536 x those of optim_rows) are put back outside the
+    timed region."""
+    import statistics
+    import torch
+    import bench_step
+    from epnet_amd import optim
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model_f = bench_step.build_model(image=True).to(dev)
+    model_c = bench_step.build_model(image=True).to(dev)
+    model_c.load_state_dict(model_f.state_dict())
+    steps = 2 * (3 + args.reps)
+    scaled = optim.FusedAdamOneCycle(model_f, steps, loss_scale="dynamic")
+    plain = optim.FusedAdamOneCycle(model_c, steps)
+    params_f, params_c = scaled.params, plain.params
+    g = torch.Generator(device=dev).manual_seed(1)
+    master = [torch.randn(p.shape, generator=g, device=dev) * (1e-3 * 65536.0) for p in params_f]
+    for p, q, m in zip(params_f, params_c, master):
+        p.grad, q.grad = m.clone(), m.clone()
+    grads_f, grads_c = [p.grad for p in params_f], [q.grad for q in params_c]
+    n = sum(p.numel() for p in params_f)
+    scale = torch.full((1,), 65536.0, device=dev)
+    tracker = torch.zeros((1,), dtype=torch.int32, device=dev)
+
+    def composed_step():
+        found = torch.full((), 0.0, dtype=torch.float32, device=dev)
+        inv = scale.double().reciprocal().float()
+        torch._amp_foreach_non_finite_check_and_unscale_(grads_c, found, inv)
+        plain.step()
+        torch._amp_update_scale_(scale, tracker, found, 2.0, 0.5, 2000)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+    sides = {"scaled": (True, True), "scaled_fused": (True, False), "scaled_composed": (False, True)}[args.optim_side]
+    passes, same = [], None
+    for _ in range(2):
+        tf, tc = [], []
+        for k in range(3 + args.reps):
+            torch._foreach_copy_(grads_f, master)
+            torch._foreach_copy_(grads_c, master)
+            torch.cuda.synchronize()
+            a = timed(scaled.step) if sides[0] else 0.0
+            b = timed(composed_step) if sides[1] else 0.0
+            if same is None and all(sides):   # one step from the same state: defined to be the same bits
+                same = all(torch.equal(p, q) for p, q in zip(params_f, params_c))
+            if k >= 3:
+                tf.append(a); tc.append(b)
+        passes.append((tf, tc))
+    shape = {"tensors": len(params_f), "parameters": n, "reps": args.reps}
+    if not all(sides):
+        side = [statistics.median(t[0] if sides[0] else t[1]) for t in passes]
+        return report("adam_onecycle_step_scaled/%s_alone" % args.optim_side, shape, statistics.median(side), n * 36 if sides[0] else 0,
+                      "side %s only (for a kernel trace); medians of the two passes: %s" % (args.optim_side, ["%.4f" % v for v in side]))
+
+    def quartiles(t):
+        q = statistics.quantiles(t, n=4)
+        return q[0], q[2]
+    rows, faster = [], True
+    for tf, tc in passes:
+        mf, mc = statistics.median(tf), statistics.median(tc)
+        lo, hi = quartiles(tc)
+        faster = faster and mf < mc - (hi - lo)
+        rows.append("scaled %.4f ms (min %.4f max %.4f), composition %.4f ms (min %.4f, quartiles %.4f .. %.4f, max %.4f), scaled lower in "
+                    "%d of %d pairs" % (mf, min(tf), max(tf), mc, min(tc), lo, hi, max(tc), sum(a < b for a, b in zip(tf, tc)), len(tf)))
+    stats = scaled.stats.tolist()
+    report("adam_onecycle_step_scaled", shape, statistics.median(passes[0][0] + passes[1][0]), n * 36,
+           "three launches, nothing read back, against unscale (torch._amp_foreach_non_finite_check_and_unscale_, with found_inf and "
+           "1 / scale made as GradScaler makes them) + the plain fused step + torch._amp_update_scale_, no host read of found_inf on "
+           "either side; pass 1: %s; pass 2: %s; below the composition by more than its interquartile range in both passes: %s; "
+           "parameters after the first step bit-equal: %s; scale %g, skipped %d, tracker %d (composition: scale %g, tracker %d)"
+           % (rows[0], rows[1], faster, same, stats[6], int(stats[7]), int(scaled.scaler_state[0]), float(scale), int(tracker)))
+
+
 def targets_rows(args, report, timeit_pair):
     """the fused RPN training targets (augmentation + labels, one launch: epnet_amd/rpn_target_layer.py) against the stock
     composition bench_step.rpn_labels (labels only, (B,N,G,3) temporaries), alternating inside one call, at 2 / 16 / 256 scenes x
@@ -850,9 +930,12 @@ def main():
     ap.add_argument("--handover-scenes", default="1,2,16,256", help="with --handover-only: the batch sizes, comma separated")
     ap.add_argument("--optim-only", action="store_true",
                     help="only the optimiser step: FusedAdamOneCycle against the stock-torch composition on the two-stream model's parameters")
-    ap.add_argument("--optim-side", default="both", choices=["both", "fused", "fused_views", "composed"],
+    ap.add_argument("--optim-side", default="both", choices=["both", "fused", "fused_views", "composed", "scaled", "scaled_fused",
+                                                             "scaled_composed"],
                     help="with --optim-only: run one side alone (what a kernel trace of launches per step needs); fused_views: the fused "
-                         "side with every gradient a view at an odd offset of one bucket")
+                         "side with every gradient a view at an odd offset of one bucket; scaled: the step with dynamic loss scaling "
+                         "against its stock composition (unscale + the plain fused step + scale update), scaled_fused / "
+                         "scaled_composed: one of those alone")
     ap.add_argument("--rows16-only", action="store_true",
                     help="only the native 16-bit SA / FP kernels against their float32 twins and the upcast composition (bf16)")
     ap.add_argument("--kitti-eval-only", action="store_true",
@@ -974,7 +1057,7 @@ def main():
     if args.loss_only:
         return loss_rows(args, report, timeit_pair)
     if args.optim_only:
-        return optim_rows(args, report)
+        return (optim_scaled_rows if args.optim_side.startswith("scaled") else optim_rows)(args, report)
     if args.targets_only:
         return targets_rows(args, report, timeit_pair)
     if args.rcnn_targets_only:

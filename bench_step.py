@@ -311,10 +311,14 @@ def main():
                     help="with --inputs raw: GT-database augmentation of the point-only loader between the validity filter and the "
                          "sampling (gt_aug_layer.prepare_scans_gt_aug on a synthetic database of 200 objects, fresh draws every step, "
                          "no host synchronisation); a pasted object has no pixels, so the flag is refused together with --image")
-    ap.add_argument("--amp", default="off", choices=["off", "bf16"],
+    ap.add_argument("--amp", default="off", choices=["off", "bf16", "fp16"],
                     help="bf16: forward under torch.autocast('cuda', torch.bfloat16) -- dense layers and this package's SA / FP operators on "
-                         "bfloat16 rows, parameters and their gradients float32 (float16 is not offered: training in it needs loss "
-                         "scaling, which FusedAdamOneCycle does not do)")
+                         "bfloat16 rows, parameters and their gradients float32. fp16: the same under torch.float16 with dynamic loss "
+                         "scaling inside the optimiser step (--optimizer fused only: FusedAdamOneCycle(loss_scale='dynamic'), the loss "
+                         "goes through scale_loss)")
+    ap.add_argument("--loss-scale", default="off", choices=["off", "guard"],
+                    help="guard: with --optimizer fused under --amp off / bf16, a static loss scale of 1.0 -- the step is skipped on the "
+                         "device when a gradient is not finite (--amp fp16 brings its own dynamic scale)")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks (one per GPU); without a torch.distributed.run environment the ranks are started as child processes")
     ap.add_argument("--launch-check", action="store_true", help="rehearse the N-rank launch only (see bench.py)")
@@ -327,6 +331,10 @@ def main():
         ap.error("--gt-aug belongs to the point-only loader: --rpn-only --inputs raw, without --image")
     if args.inputs == "raw" and (not args.rpn_only or args.image or args.infer):
         ap.error("--inputs raw starts the point-stream RPN step (--rpn-only, without --image) from raw scans")
+    if (args.amp == "fp16" or args.loss_scale == "guard") and (args.optimizer != "fused" or args.infer):
+        ap.error("--amp fp16 and --loss-scale guard are the fused optimiser's loss scaling: pass --optimizer fused")
+    if args.amp == "fp16" and args.loss_scale == "guard":
+        ap.error("--amp fp16 scales dynamically; --loss-scale guard belongs to --amp off / bf16")
     if args.infer and args.image:
         ap.error("--infer times the point-stream RPN stage; the two-stream backbone (--image) is timed by the training step only")
     from epnet_amd import scene_shard
@@ -363,7 +371,8 @@ def main():
     total_steps = args.warmup + args.steps + 8                         # the instrumented pass takes up to 5 more
     if args.optimizer == "fused":
         from epnet_amd import optim
-        opt = optim.FusedAdamOneCycle(model.module if hasattr(model, "module") else model, total_steps)
+        loss_scale = "dynamic" if args.amp == "fp16" else 1.0 if args.loss_scale == "guard" else None
+        opt = optim.FusedAdamOneCycle(model.module if hasattr(model, "module") else model, total_steps, loss_scale=loss_scale)
         zero_grad = opt.zero_grad                                      # nothing to do: the step leaves the gradients zero, in place
     elif args.optimizer == "composed":
         from bench_ops import ComposedAdamOneCycle
@@ -423,6 +432,7 @@ def main():
 
     phases = {}
     last_out = {}
+    scaled = args.optimizer == "fused" and opt.scale is not None
 
     def one(timed):
         events = [("start", torch.cuda.Event(enable_timing=True))]
@@ -436,11 +446,11 @@ def main():
         step_xyz, step_gts = step_inputs()
         if raw is not None and timed:
             mark("inputs")
-        with torch.autocast("cuda", torch.bfloat16, enabled=args.amp == "bf16"):
+        with torch.autocast("cuda", torch.float16 if args.amp == "fp16" else torch.bfloat16, enabled=args.amp != "off"):
             loss, out = run_step(model, layers, step_xyz, step_gts, mark if timed else None, image, xy, args.rpn_only)
         if timed:                                              # the line carries the terms of the last TIMED step
             last_out.update({k: v for k, v in out.items() if k in ("rpn_loss", "rcnn_loss")})
-        loss.backward()
+        (opt.scale_loss(loss) if scaled else loss).backward()
         mark("backward")
         opt.step()
         mark("optimizer")
@@ -548,10 +558,11 @@ def main():
                           "devices": [r_["device"] for r_ in per_rank], "rehearsal": bool(args.rehearsal),
                           "per_rank_ms_per_step": {"min": min(r_["ms_per_step"] for r_ in per_rank),
                                                    "max": max(r_["ms_per_step"] for r_ in per_rank)},
-                          "loss": last, "data": "synthetic", "dtype": "f32" if args.amp == "off" else "bf16 autocast (parameters f32)", **({} if raw is None else {"inputs": "raw"}),
+                          "loss": last, "data": "synthetic", "dtype": "f32" if args.amp == "off" else "%s autocast (parameters f32)" % args.amp, **({} if raw is None else {"inputs": "raw"}),
                           **({} if not args.gt_aug else {"gt_aug": True}),
                           **({} if args.optimizer == "sgd" else {"optimizer": args.optimizer}),
                           **({} if args.optimizer != "fused" else {"optimizer_stats": dict(zip(optim.optim_cuda.STATS_NAMES, opt.stats.tolist()))}),
+                          **({} if not scaled else {"loss_scale": dict(opt.scaler_state_dict(), mode="dynamic" if args.amp == "fp16" else "guard")}),
                           **({} if args.loss == "placeholder" else {"loss_mode": args.loss, "loss_terms": {
                               n_: round(float(v), 6) for r_ in last_out.values() for n_, v in zip(r_.names, r_.terms.tolist())}}),
                           "note": "phase_ms from HIP events (%s); "

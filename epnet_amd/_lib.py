@@ -116,6 +116,8 @@ SIGNATURES = {
     "epnet_adam_onecycle_workspace_bytes": (_sz, [ctypes.c_longlong]),
     "epnet_adam_onecycle_step": (_i, [_i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _d, _d, _d, _i, _vp, _vp,
                                       _vp, _vp, _vp, _sz, _vp]),
+    "epnet_adam_onecycle_step_scaled": (_i, [_i, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _d, _d, _d, _i, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _d, _d, ctypes.c_longlong, _d, _vp, _sz, _vp]),
     "epnet_rpn_targets": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "epnet_scan_prepare_workspace_bytes": (_sz, [_i, _i, _i]),
     "epnet_scan_prepare": (_i, [_i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -92,10 +92,21 @@ class FusedAdamOneCycle:
     is the only place that may synchronise; inside a graph capture it raises instead (run a step eagerly first).
 
     ``stats``: float64 (8) on the device -- total_norm, coef, lr, mom, the step used, 1 past ``total_steps`` -- as of the last
-    step; read it whenever logging is due."""
+    step; read it whenever logging is due.
+
+    ``loss_scale``: None (the default) is the plain step. ``"dynamic"`` is ``torch.amp.GradScaler``'s rule inside the same three
+    launches (``epnet_adam_onecycle_step_scaled``): back-propagate ``opt.scale_loss(loss)``, and ``step()`` unscales the
+    gradients as it reads them, skips the step when one of them is not finite (parameters, moments and the step counter stay,
+    the gradients are still zeroed), multiplies the scale by ``backoff_factor`` (not below ``min_scale``) then, and by
+    ``growth_factor`` after ``growth_interval`` applied steps in a row. A float is a static scale: it never moves, non-finite
+    steps are still skipped; ``1.0`` is the guard for bfloat16 / float32 training. Nothing is read back: the scale (``opt.scale``),
+    the growth tracker and the number of skipped steps live on the device, ``stats[6]`` is the scale the last step used and
+    ``stats[7]`` the steps skipped so far. Parameters and gradients stay float32 (what ``torch.autocast`` gives); one scale
+    serves all groups."""
 
     def __init__(self, model_or_params, total_steps, lr_max=0.002, moms=(0.95, 0.85), div_factor=10.0, pct_start=0.4, wd=0.001,
-                 beta2=0.99, eps=1e-8, grad_norm_clip=1.0, zero_grads=True):
+                 beta2=0.99, eps=1e-8, grad_norm_clip=1.0, zero_grads=True, loss_scale=None, init_scale=65536.0, growth_factor=2.0,
+                 backoff_factor=0.5, growth_interval=2000, min_scale=1.0):
         if isinstance(model_or_params, nn.Module):
             groups = layer_groups(model_or_params)
         else:
@@ -127,6 +138,64 @@ class FusedAdamOneCycle:
         self.stats = torch.zeros((optim_cuda.STATS,), dtype=torch.float64, device=self.device)
         self._signature = None
         self._tables = None
+        self._init_scaler(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval, min_scale)
+
+    # ---- loss scaling -------------------------------------------------------------------------------------------------------
+    def _init_scaler(self, loss_scale, init_scale, growth_factor, backoff_factor, growth_interval, min_scale):
+        self.loss_scale = loss_scale
+        self.scale = self.scaler_state = None
+        if loss_scale is None:
+            return
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError("FusedAdamOneCycle: loss_scale is None, \"dynamic\" or a number, got %r" % (loss_scale,))
+            start, interval = float(init_scale), int(growth_interval)
+            if interval < 1:
+                raise ValueError("FusedAdamOneCycle: growth_interval must be at least 1 (got %r); a number as loss_scale is a "
+                                 "static scale" % (growth_interval,))
+        else:
+            start, interval = float(loss_scale), 0
+        growth_factor, backoff_factor, min_scale = float(growth_factor), float(backoff_factor), float(min_scale)
+        fmax = float(np.finfo(np.float32).max)
+        for name, value in (("growth_factor", growth_factor), ("backoff_factor", backoff_factor), ("min_scale", min_scale),
+                            ("the scale", start)):
+            if not 0 < value <= fmax:                   # also refuses NaN
+                raise ValueError("FusedAdamOneCycle: %s must be positive and finite in float32, got %r" % (name, value))
+        if growth_factor < 1:
+            raise ValueError("FusedAdamOneCycle: growth_factor must be at least 1, got %r" % growth_factor)
+        if backoff_factor > 1:
+            raise ValueError("FusedAdamOneCycle: backoff_factor must be at most 1, got %r" % backoff_factor)
+        if interval and start < min_scale:
+            raise ValueError("FusedAdamOneCycle: init_scale %r is below min_scale %r" % (start, min_scale))
+        self.growth_factor, self.backoff_factor, self.growth_interval, self.min_scale = growth_factor, backoff_factor, interval, min_scale
+        self.scale = torch.full((1,), start, dtype=torch.float32, device=self.device)
+        self.scaler_state = torch.zeros((2,), dtype=torch.int64, device=self.device)   # growth tracker, steps skipped
+
+    def scale_loss(self, loss):
+        """``loss * scale`` as one stock multiply by the device tensor: differentiable, capturable, nothing read back"""
+        if self.scale is None:
+            raise RuntimeError("FusedAdamOneCycle.scale_loss: this optimiser was built with loss_scale=None")
+        return loss * self.scale
+
+    def scaler_state_dict(self):
+        """``torch.amp.GradScaler.state_dict()``'s keys plus ``skipped``; reads the device (synchronises)"""
+        if self.scale is None:
+            raise RuntimeError("FusedAdamOneCycle.scaler_state_dict: this optimiser was built with loss_scale=None")
+        tracker, skipped = self.scaler_state.tolist()
+        return {"scale": float(self.scale.item()), "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": int(tracker), "skipped": int(skipped)}
+
+    def load_scaler_state_dict(self, state):
+        """the scale and the growth tracker of ``scaler_state_dict()`` or of a ``GradScaler.state_dict()`` (``skipped`` is 0
+        where missing). The factors and the interval stay the constructor's: whether the scale is static is not a checkpoint's
+        to decide."""
+        if self.scale is None:
+            raise RuntimeError("FusedAdamOneCycle.load_scaler_state_dict: this optimiser was built with loss_scale=None")
+        scale = float(state["scale"])
+        if not 0 < scale <= float(np.finfo(np.float32).max):
+            raise ValueError("load_scaler_state_dict: scale %r" % scale)
+        self.scale.fill_(scale)
+        self.scaler_state.copy_(torch.tensor([int(state.get("_growth_tracker", 0)), int(state.get("skipped", 0))], dtype=torch.int64))
 
     # ---- the tables ---------------------------------------------------------------------------------------------------------
     def _current_signature(self):
@@ -185,8 +254,14 @@ class FusedAdamOneCycle:
         tt, ct, max_numel, ws, live, stepped = self._tables
         if tt.shape[0] == 0:
             return
-        optim_cuda.adam_onecycle_step_gpu(tt, ct, max_numel, self.rows, self.grad_norm_clip, self.eps, self.beta2, self.zero_grads,
-                                          self.counter, self.exp_avg, self.exp_avg_sq, self.stats, ws)
+        if self.scale is None:
+            optim_cuda.adam_onecycle_step_gpu(tt, ct, max_numel, self.rows, self.grad_norm_clip, self.eps, self.beta2, self.zero_grads,
+                                              self.counter, self.exp_avg, self.exp_avg_sq, self.stats, ws)
+        else:
+            optim_cuda.adam_onecycle_step_scaled_gpu(tt, ct, max_numel, self.rows, self.grad_norm_clip, self.eps, self.beta2,
+                                                     self.zero_grads, self.counter, self.exp_avg, self.exp_avg_sq, self.stats,
+                                                     self.scale, self.scaler_state, self.growth_factor, self.backoff_factor,
+                                                     self.growth_interval, self.min_scale, ws)
         for i in stepped:                  # these now have moments (only once the launch went through)
             self._has_state[i] = True
         torch._C._increment_version(live)  # the kernels wrote the parameters (and zeroed the gradients) through raw pointers
@@ -211,8 +286,8 @@ class FusedAdamOneCycle:
         at = min(max(step - 1, 0), self.total_steps - 1)
         state = {}
         for i in range(len(self.params)):
-            if self._has_state[i]:
-                state[i] = {"step": torch.tensor(float(step)), "exp_avg": self._piece(self.exp_avg, i).clone(),
+            if self._has_state[i] and step > 0:        # step 0 with state: every step so far was skipped (loss scaling)
+                state[i] ={"step": torch.tensor(float(step)), "exp_avg": self._piece(self.exp_avg, i).clone(),
                             "exp_avg_sq": self._piece(self.exp_avg_sq, i).clone()}
         groups, first = [], 0
         for g in self.groups:

@@ -15,8 +15,8 @@ backward, ``three_interpolate`` forward. UPCAST route (the float32 kernel, then 
 ``grouping_operation``, the gradients of ``group_linear`` (``grad_z``; ``grad_w`` / ``grad_b`` come back float32, the
 parameters' type) and of ``three_interpolate``, ``group_concat`` / ``group_concat_multi`` / ``QueryAndGroup`` (float32 out with
 ``use_xyz=True`` -- the stock promotion of ``cat(fp32 xyz, T features)`` -- and ``T`` with ``use_xyz=False``) and every
-deterministic (``_det``) twin. float16 is for inference and single ops: training in it needs loss scaling, which
-``FusedAdamOneCycle`` does not do; train under ``torch.autocast("cuda", torch.bfloat16)``.
+deterministic (``_det``) twin. Training in float16 needs loss scaling: ``FusedAdamOneCycle(loss_scale="dynamic")`` does it
+inside the optimiser step; bfloat16 needs none.
 """
 import os
 import threading

@@ -957,6 +957,37 @@ int epnet_adam_onecycle_step(int tensors, long long chunks, long long max_numel,
                              double b2, int zero_grads, long long *counter, float *exp_avg, float *exp_avg_sq,
                              double *stats, void *workspace, size_t workspace_bytes, epnet_stream_t stream);
 
+/* The same step with loss scaling and non-finite step skipping: still three launches, nothing read back, and every value that
+ * changes from step to step (the scale, its growth tracker, the skip count) read from device memory, so a captured graph replays
+ * it. The gradients are those of loss * scale; torch.amp.GradScaler in front of the step above costs one more read-modify-write
+ * pass over every gradient and a host read of found_inf.
+ *   scale (1) fp32, scaler_state (2) i64 = [growth_tracker, skipped_total], both read and written.
+ * Unscaling: inv = (float)(1.0 / (double)scale[0]); every gradient enters the step as gu = g * inv, rounded to fp32, and the step
+ * is the one above on gu: the norm is the float64 sum of (double)gu * (double)gu in the same order, coef comes from that norm, and
+ * Adam uses g' = gu coef. The result is "g *= inv in stock fp32, then epnet_adam_onecycle_step", bit for bit, for any scale (not
+ * only powers of two).
+ * Detection: the step is non-finite iff the reduced float64 sum of squares is not finite -- a NaN or an infinity in any
+ * gradient, or an overflow of g * inv; squares of finite floats cannot overflow a double. No extra pass, no atomics.
+ * A non-finite step is skipped: parameters, exp_avg and exp_avg_sq keep their bits (no weight decay either, also for a tensor
+ * without a gradient), the counter does not advance -- the schedule's row and Adam's bias corrections count APPLIED steps, as
+ * with GradScaler, which skips optimizer.step() --, skipped_total += 1, and with zero_grads != 0 the gradients are still stored
+ * as zeros.
+ * Scale update, after the scale's value was taken for this step: torch._amp_update_scale_'s rule, the product taken in double
+ * and rounded once to fp32 as there. Non-finite step: scale = max((float)(scale * backoff_factor), (float)min_scale), tracker = 0.
+ * Otherwise tracker += 1, and when it equals growth_interval: scale = (float)(scale * growth_factor) if that is finite (else the
+ * scale stays), tracker = 0. growth_interval == 0 is a static scale: detection, skipping and the two counts only, the scale is
+ * never written (a static scale of 1.0 is a non-finite guard for bf16 / fp32 training).
+ *   stats: [0..5] as above; on a skipped step [0] is the non-finite norm, [1] is 0 and [2..5] describe the row that would have
+ *     been used; [6] the scale this step used, [7] skipped_total after the step.
+ * Errors as above, and EPNET_EINVAL for growth_factor < 1, backoff_factor outside (0, 1], growth_interval < 0, min_scale not
+ * > 0 (or any of them NaN or beyond fp32), a NULL scale or scaler_state. Workspace as above. */
+int epnet_adam_onecycle_step_scaled(int tensors, long long chunks, long long max_numel, const epnet_optim_tensor *tensor_table,
+                                    const int *chunk_table, const float *rows, long long total_steps, double clip, double eps,
+                                    double b2, int zero_grads, long long *counter, float *exp_avg, float *exp_avg_sq,
+                                    double *stats, float *scale, long long *scaler_state, double growth_factor,
+                                    double backoff_factor, long long growth_interval, double min_scale, void *workspace,
+                                    size_t workspace_bytes, epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
