@@ -4,7 +4,8 @@ iou3d (rotated overlap / IoU, both NMS flavours), roipool3d, three_nn / three_in
 gradient ops, at the shapes of the reference's rcnn_online step. One JSON line per op:
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
-    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only | --gt-aug-only | --handover-only]
+    python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only | --gt-aug-only | --handover-only |
+                         --image-head-only]
 """
 import argparse
 import json
@@ -908,9 +909,82 @@ def gt_aug_rows(args, report, timeit_pair):
                               "(numpy)" % ((t1 - t0) * 1e3, (t2 - t1) * 1e3)}), flush=True)
 
 
+def image_head_rows(args, timeit_pair):
+    """the end of the two-stream backbone alone at the yaml's widths, 384 x 1280, 16384 points per scene: the existing
+    dense lines (DeConv x 4, concatenation, 1x1 convolution + batch norm + ReLU, Feature_Gather -- sampler="hip") against
+    li_fusion.image_head_at_points, eval mode under no_grad. Alternating inside one call, median of --reps by HIP events, two
+    passes; "faster" = below the dense side in both passes by more than the dense side's own spread between its passes. Peak
+    allocated bytes of one call of each side, above what the inputs and weights hold."""
+    import torch
+    import torch.nn.functional as F
+    from epnet_amd import li_fusion, rpn_backbone
+    dev = torch.device("cuda:0")
+    cfg = rpn_backbone.BackboneConfig()
+    h, w, n = 384, 1280, 16384
+    torch.manual_seed(0)
+    deconvs = torch.nn.ModuleList([rpn_backbone.UpsampleDeConv(c, r, kernel_size=k, stride=k)
+                                   for c, r, k in zip(cfg.img_channels[1:], cfg.deconv_reduce, cfg.deconv_kernels)])
+    quarter = cfg.img_features_channel // 4
+    conv, bn = torch.nn.Conv2d(sum(cfg.deconv_reduce), quarter, kernel_size=1), torch.nn.BatchNorm2d(quarter)
+    with torch.no_grad():
+        bn.running_mean.normal_(0.0, 0.3)
+        bn.running_var.uniform_(0.5, 2.0)
+    deconvs, conv, bn = deconvs.to(dev).eval(), conv.to(dev).eval(), bn.to(dev).eval()
+    packed = li_fusion.pack_image_head(deconvs, conv, bn)
+    g = torch.Generator().manual_seed(1)
+    for bsz in [int(v) for v in args.image_head_scenes.split(",")]:
+        maps = [torch.randn((bsz, c, h // k, w // k), generator=g).to(dev) for c, k in zip(cfg.img_channels[1:], cfg.deconv_kernels)]
+        xy = (torch.rand((bsz, n, 2), generator=g) * 2.0 - 1.0).to(dev)
+        assert li_fusion.supports_image_head_at_points(deconvs, conv, bn, maps)
+
+        def dense():
+            with torch.no_grad():
+                up = torch.cat([deconvs[i](maps[i]) for i in range(len(deconvs))], dim=1)
+                img_fusion = F.relu(bn(conv(up)))
+                return li_fusion.Feature_Gather(img_fusion, xy)
+
+        def points():
+            return li_fusion.image_head_at_points(maps, packed, xy)
+
+        def peak(fn):
+            fn()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            held = torch.cuda.memory_allocated(dev)
+            out = fn()
+            torch.cuda.synchronize()
+            top = torch.cuda.max_memory_allocated(dev) - held
+            del out
+            return int(top)
+
+        shape = {"B": bsz, "N": n, "H": h, "W": w, "C": cfg.img_channels[1:], "R": cfg.deconv_reduce, "q": quarter}
+        if args.image_head_side != "both":
+            fn = points if args.image_head_side == "points" else dense
+            for _ in range(args.reps):
+                fn()
+            torch.cuda.synchronize()
+            print(json.dumps({"op": "image_head/%s_alone" % args.image_head_side, "shape": shape, "calls": args.reps}), flush=True)
+            continue
+        diff = float((dense() - points()).abs().max())
+        peak_d, peak_p = peak(dense), peak(points)
+        (d1, p1), (d2, p2) = timeit_pair(dense, points), timeit_pair(dense, points)
+        spread = abs(d1 - d2)
+        faster = p1 < d1 and p2 < d2 and min(d1 - p1, d2 - p2) > spread
+        print(json.dumps({"op": "image_head", "shape": shape, "ms_dense": [round(d1, 4), round(d2, 4)], "ms_points": [round(p1, 4), round(p2, 4)],
+                          "dense_spread_ms": round(spread, 4), "points_is_faster": bool(faster), "peak_bytes_dense": peak_d,
+                          "peak_bytes_points": peak_p, "max_abs_diff": diff, "reps": args.reps}), flush=True)
+        del maps, xy
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--image-head-only", action="store_true",
+                    help="only the two-stream backbone's image head: the dense lines against li_fusion.image_head_at_points")
+    ap.add_argument("--image-head-side", default="both", choices=["both", "points", "dense"],
+                    help="with --image-head-only: run one side alone, --reps calls per size (for a kernel trace)")
+    ap.add_argument("--image-head-scenes", default="1,2,16", help="with --image-head-only: the batch sizes, comma separated")
     ap.add_argument("--gt-aug-only", action="store_true",
                     help="only GT-database augmentation: gt_aug_layer.prepare_scans_gt_aug against scan_layer.prepare_scans on the same scans")
     ap.add_argument("--gt-aug-side", default="both", choices=["both", "fused"],
@@ -1054,6 +1128,8 @@ def main():
 
     if args.stage2_only:
         return stage2_infer()
+    if args.image_head_only:
+        return image_head_rows(args, timeit_pair)
     if args.loss_only:
         return loss_rows(args, report, timeit_pair)
     if args.optim_only:

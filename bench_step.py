@@ -8,6 +8,7 @@
     python bench_step.py                                      # the point stream alone (round-1 figure)
     python bench_step.py --infer [--two-stage]                # inference latency: the RPN stage [and the whole detector]
     python bench_step.py --infer --two-stage --proposals fused   # the same with the one-call RPN hand-over (epnet_rpn_handover)
+    python bench_step.py --infer --two-stage --image [--image-head points]   # the two-stream detector; points: the image head at the taps only
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench_step.py --gpus N   # scene-parallel, RCCL
 
 What is timed (forward + backward + optimiser step -- SGD unless --optimizer says otherwise --, `--batch` scenes per GPU):
@@ -50,12 +51,13 @@ RCNN_MLPS = [[128, 128, 128], [128, 128, 256], [256, 256, 512]]
 PROPOSALS_DEFAULT = "composed"       # --proposals: the stock decoding + sort in front of epnet_rpn_proposals
 
 
-def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder"):
+def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder", image_head="dense"):
     """the two-stage model; scale > 1 divides the pyramid's point counts (small test configurations); image: the
     two-stream backbone with LI-Fusion (configs 3 / 4) instead of the point stream alone; loss: "placeholder" (sums of squares),
     "reference" (the real losses, fused: epnet_amd.loss_utils) or "composed" (the real losses as the reference composes them from
     stock torch calls, with its mask indexing and .item() reads: bench_ops.composed_rpn_loss / composed_rcnn_loss); the real
-    losses read the RPN labels from model.rpn_labels = rpn_labels(xyz, gt_boxes3d)"""
+    losses read the RPN labels from model.rpn_labels = rpn_labels(xyz, gt_boxes3d); image_head: the two-stream backbone's
+    "dense" (default) or "points" (inference: the image head under the bilinear taps only, rpn_backbone.Pointnet2MSG)"""
     import torch
     import torch.nn as nn
     from epnet_amd import pytorch_utils as pt_utils, rpn_backbone
@@ -91,7 +93,7 @@ def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="plac
             super().__init__()
             # lib/net/pointnet2_msg.py:126-259 (rpn.py:19: input_channels = 0, the yaml has USE_INTENSITY False)
             self.backbone = rpn_backbone.Pointnet2MSG(input_channels=0, config=rpn_backbone.BackboneConfig(li_fusion=image),
-                                                      sampler=sampler, scale=scale, pyramid=PYRAMID)
+                                                      sampler=sampler, scale=scale, pyramid=PYRAMID, image_head=image_head)
             self.two_stream = image
             self.rpn_cls = nn.Sequential(pt_utils.Conv1d(128, 128, bn=True), pt_utils.Conv1d(128, 1, activation=None))
             self.rpn_reg = nn.Sequential(pt_utils.Conv1d(128, 128, bn=True), pt_utils.Conv1d(128, rpn_channels, activation=None))
@@ -187,13 +189,22 @@ def synthetic_batch(batch, points, seed, device):
     return xyz, gts.to(device)
 
 
-def infer(args, model, proposal_layer, xyz):
-    """inference latency, eager launches against one HIP-graph replay: the RPN stage and, with --two-stage, the whole detector"""
+def infer(args, model, proposal_layer, xyz, image=None, xy=None):
+    """inference latency, eager launches against one HIP-graph replay: the RPN stage and, with --two-stage, the whole detector;
+    image / xy: the two-stream backbone's inputs (--image)"""
     import torch
     model.eval()
+    two_stream = {"image": True, "image_head": args.image_head} if image is not None else {}
+    if image is not None:
+        # the image stream's convolutions: at 2 scenes the dense library's default choice sums in an order that changes from run to
+        # run, so two EAGER runs of the RPN stage already differ (graph_equals_eager false with either head, measured); as for the
+        # RCNN heads below, its deterministic algorithms are asked for, for the comparison to mean something
+        torch.backends.cudnn.deterministic = True
+        two_stream["dense_layers_deterministic"] = True
 
     def rpn():
-        _, feats = model.backbone(xyz)
+        # the backbone normalises xy in place: a fresh copy per call
+        _, feats = model.backbone(xyz, image, xy.clone()) if image is not None else model.backbone(xyz)
         cls = model.rpn_cls(feats).transpose(1, 2).contiguous()
         reg = model.rpn_reg(feats).transpose(1, 2).contiguous()
         return feats, cls[:, :, 0].contiguous(), reg
@@ -231,7 +242,8 @@ def infer(args, model, proposal_layer, xyz):
     ms_eager, ms_graph, same, _ = eager_and_graph(stage)
     print(json.dumps({"metric": "RPN-stage inference latency (backbone + heads + proposal layer, eval mode)", "scenes": args.batch,
                       "points_per_scene": args.points, "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3),
-                      "graph_equals_eager": bool(same), "proposals": args.proposals, "dtype": "f32", "data": "synthetic"}), flush=True)
+                      "graph_equals_eager": bool(same), "proposals": args.proposals, "dtype": "f32", "data": "synthetic",
+                      **two_stream}), flush=True)
     if not args.two_stage:
         return
     # the whole detector (lib/net/point_rcnn.py:33-47 + the eval branch of lib/net/rcnn_net.py:138-164 + tools/eval_rcnn.py:555-583,
@@ -267,7 +279,7 @@ def infer(args, model, proposal_layer, xyz):
                       "scenes": args.batch, "points_per_scene": args.points, "rois_per_scene": int(out[0].shape[1]),
                       "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3), "graph_equals_eager": bool(same),
                       "detections": counts, "dense_layers_deterministic": True, "proposals": args.proposals, "dtype": "f32",
-                      "data": "synthetic"}), flush=True)
+                      "data": "synthetic", **two_stream}), flush=True)
 
 
 def main():
@@ -285,6 +297,10 @@ def main():
     ap.add_argument("--image", action="store_true",
                     help="two-stream backbone: (B,3,384,1280) image ~N(0,1), pixel coordinates ~U[0,1280)xU[0,384), LI-Fusion with "
                          "image attention (BASELINE configs 3 and 4; 15.7 M parameters = 62.7 MB of gradients)")
+    ap.add_argument("--image-head", default="dense", choices=["dense", "points"],
+                    help="with --image: the end of the image stream -- the full-resolution fusion map sampled at the points (default) "
+                         "or, in inference, the head evaluated under the bilinear taps only (li_fusion.image_head_at_points); the "
+                         "training steps run the dense lines either way")
     ap.add_argument("--rpn-only", action="store_true", help="config 3: forward + backward of backbone + RPN heads only")
     ap.add_argument("--sampler", default="hip", choices=["hip", "stock"],
                     help="point-to-pixel sampler: this package's Feature_Gather or stock torch.gather + grid_sample")
@@ -335,8 +351,8 @@ def main():
         ap.error("--amp fp16 and --loss-scale guard are the fused optimiser's loss scaling: pass --optimizer fused")
     if args.amp == "fp16" and args.loss_scale == "guard":
         ap.error("--amp fp16 scales dynamically; --loss-scale guard belongs to --amp off / bf16")
-    if args.infer and args.image:
-        ap.error("--infer times the point-stream RPN stage; the two-stream backbone (--image) is timed by the training step only")
+    if args.image_head != "dense" and not args.image:
+        ap.error("--image-head belongs to the two-stream backbone: pass --image")
     from epnet_amd import scene_shard
     code = scene_shard.launch_or_continue(args.gpus, os.path.abspath(__file__), sys.argv[1:])
     if code is not None:
@@ -365,7 +381,7 @@ def main():
             dist.init_process_group(backend)
     torch.manual_seed(1 + rank)
     np.random.seed(1 + rank)
-    model = build_model(image=args.image, sampler=args.sampler, loss=args.loss).to(device)
+    model = build_model(image=args.image, sampler=args.sampler, loss=args.loss, image_head=args.image_head).to(device)
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local], find_unused_parameters=False)
     total_steps = args.warmup + args.steps + 8                         # the instrumented pass takes up to 5 more
@@ -394,7 +410,7 @@ def main():
         xy = (torch.rand((args.batch, args.points, 2), generator=g) * torch.tensor([1280.0, 384.0])).to(device)
 
     if args.infer:
-        return infer(args, model.module if hasattr(model, "module") else model, layers[0], xyz)
+        return infer(args, model.module if hasattr(model, "module") else model, layers[0], xyz, image, xy)
     raw = None
     if args.inputs == "raw":
         from epnet_amd import rpn_target_layer, scan_layer, synth

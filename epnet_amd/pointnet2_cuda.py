@@ -590,3 +590,50 @@ def feature_gather_grad_wrapper(b, c, h, w, n, align_corners, grad_out, xy, grad
         _lib.check(_lib.lib().epnet_feature_gather_grad(b, c, h, w, n, int(bool(align_corners)), pg, px, pf, s), "feature_gather_grad")
     return 1
 
+
+
+def _int_array(values):
+    import ctypes
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def image_head_points_workspace_bytes(b, n, h, w, chans, kernels, reduce, q):
+    """scratch of image_head_points_wrapper for these shapes (0: empty problem or outside what the kernels support)"""
+    return int(_lib.lib().epnet_image_head_points_workspace_bytes(b, n, h, w, len(chans), _int_array(chans), _int_array(kernels),
+                                                                  _int_array(reduce), q))
+
+
+@writes("out")
+def image_head_points_wrapper(b, n, h, w, chans, kernels, reduce, maps, weights, q, wf, shift, xy, align_corners, out,
+                              workspace=None):
+    """LI-Fusion's image head at the points only (include/epnet_ops.h: epnet_image_head_points; not in the reference
+    extension). maps / weights: one tensor per level; workspace (optional): a uint8 tensor the caller keeps, at least
+    image_head_points_workspace_bytes(...) bytes -- otherwise scratch comes from torch's caching allocator"""
+    import ctypes
+    levels = len(chans)
+    if not (levels == len(kernels) == len(reduce) == len(maps) == len(weights)):
+        raise RuntimeError("image_head_points: one entry per level in chans, kernels, reduce, maps and weights")
+    sum_r = sum(int(r) for r in reduce)
+    pm, pw = [], []
+    for l in range(levels):
+        pm.append(dev_ptr(maps[l], "maps[%d]" % l, _F))
+        pw.append(dev_ptr(weights[l], "weights[%d]" % l, _F))
+        need(maps[l], b * chans[l] * (h // kernels[l]) * (w // kernels[l]), "maps[%d]" % l)
+        need(weights[l], kernels[l] * kernels[l] * chans[l] * reduce[l], "weights[%d]" % l)
+    pf, ps, px, po = dev_ptr(wf, "wf", _F), dev_ptr(shift, "shift", _F), dev_ptr(xy, "xy", _F), dev_ptr(out, "out", _F)
+    need(wf, q * sum_r, "wf"); need(shift, q, "shift"); need(xy, b * n * 2, "xy"); need(out, b * q * n, "out")
+    l = _lib.lib()
+    ac, ak, ar = _int_array(chans), _int_array(kernels), _int_array(reduce)
+    ws_bytes = int(l.epnet_image_head_points_workspace_bytes(b, n, h, w, levels, ac, ak, ar, q))
+    am, aw = (ctypes.c_void_p * levels)(*pm), (ctypes.c_void_p * levels)(*pw)
+    with on_device_of(xy) as s:
+        if workspace is None:
+            ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=xy.device)
+            given = ws_bytes
+        else:
+            ws, given = workspace, workspace.numel()
+            if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != xy.device:
+                raise RuntimeError("image_head_points workspace: a contiguous uint8 tensor on the tensors' device")
+        _lib.check(l.epnet_image_head_points(b, n, h, w, levels, ac, ak, ar, am, aw, q, pf, ps, px, int(bool(align_corners)), po,
+                                             ws.data_ptr(), given, s), "image_head_points")
+    return 1

@@ -13,6 +13,11 @@ global ``cfg`` (defaults = tools/cfgs/LI_Fusion_with_attention_use_ce_loss.yaml:
 ``sampler``: "hip" = this package's ``Feature_Gather`` with the xy gather over the FPS indices folded in; "stock" = the
 reference's own two steps, ``torch.gather`` + ``torch.nn.functional.grid_sample`` (``align_corners=True``: the
 reference was written for torch <= 1.2, which behaved that way) -- the yardstick of tests/test_two_stream.py.
+
+``image_head``: "dense" (default) = the reference's end of the forward, the full-resolution fusion map sampled at the points;
+"points" = for inference, ``li_fusion.image_head_at_points`` evaluates that head under the bilinear taps only.
+It is taken only in eval mode, on the GPU, on float32 maps (not under autocast), for a supported configuration and when no
+gradient is needed; in every other case "points" runs exactly the dense lines.
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -132,13 +137,16 @@ def stock_feature_gather(feature_map, xy):
 
 
 class Pointnet2MSG(nn.Module):
-    def __init__(self, input_channels=0, use_xyz=True, config: BackboneConfig = None, sampler="hip", scale=1, pyramid=True):
+    def __init__(self, input_channels=0, use_xyz=True, config: BackboneConfig = None, sampler="hip", scale=1, pyramid=True,
+                 image_head="dense"):
         """scale > 1 divides the pyramid's point counts (small test configurations); pyramid: sample all levels up front on
-        a side stream (pointnet2_utils.sample_pyramid)"""
+        a side stream (pointnet2_utils.sample_pyramid); image_head: see the module's docstring"""
         super().__init__()
         cfg = self.cfg = config or BackboneConfig()
         assert sampler in ("hip", "stock")
-        self.sampler, self.pyramid = sampler, pyramid
+        assert image_head in ("dense", "points")
+        self.sampler, self.pyramid, self.image_head = sampler, pyramid, image_head
+        self._packed_head = None                   # li_fusion.pack_image_head's result: a cache, not part of the state_dict
         self.SA_modules = nn.ModuleList()
         channel_in, skips = input_channels, [input_channels]
         for k in range(len(cfg.npoints)):
@@ -178,6 +186,20 @@ class Pointnet2MSG(nn.Module):
         picked = torch.gather(xy, 1, fps_idx.long().unsqueeze(-1).repeat(1, 1, 2))
         return stock_feature_gather(feature_map, picked), picked
 
+    def _head_at_points(self, maps, xy):
+        """the "points" image head when every condition of the module's docstring holds, else None"""
+        if self.image_head != "points" or self.training or not xy.is_cuda or torch.is_autocast_enabled():
+            return None
+        if not all(m.is_cuda and m.dtype == torch.float32 for m in maps):
+            return None
+        if torch.is_grad_enabled() and (any(m.requires_grad for m in maps) or xy.requires_grad or any(
+                p.requires_grad for mod in (self.DeConv, self.image_fusion_conv, self.image_fusion_bn) for p in mod.parameters())):
+            return None
+        if not li_fusion.supports_image_head_at_points(self.DeConv, self.image_fusion_conv, self.image_fusion_bn, maps):
+            return None
+        self._packed_head = li_fusion.pack_image_head(self.DeConv, self.image_fusion_conv, self.image_fusion_bn, self._packed_head)
+        return li_fusion.image_head_at_points(maps, self._packed_head, xy)
+
     def forward(self, pointcloud, image=None, xy=None):
         """pointcloud (B,N,3+C), image (B,3,H,W), xy (B,N,2) pixel coordinates -- normalised to [-1,1] IN PLACE, as the
         reference does (:205-208): hand over a tensor you do not need again. Returns (xyz (B,N,3), features (B,128,N))"""
@@ -205,8 +227,10 @@ class Pointnet2MSG(nn.Module):
         for i in range(-1, -(len(self.FP_modules) + 1), -1):
             l_feat[i - 1] = self.FP_modules[i](l_xyz[i - 1], l_xyz[i], l_feat[i - 1], l_feat[i])
         if fuse:
-            up = torch.cat([self.DeConv[i](img[i + 1]) for i in range(len(self.DeConv))], dim=1)
-            img_fusion = F.relu(self.image_fusion_bn(self.image_fusion_conv(up)))
-            full = (li_fusion.Feature_Gather(img_fusion, xy) if self.sampler == "hip" else stock_feature_gather(img_fusion, xy))
+            full = self._head_at_points(img[1:], xy)
+            if full is None:
+                up = torch.cat([self.DeConv[i](img[i + 1]) for i in range(len(self.DeConv))], dim=1)
+                img_fusion = F.relu(self.image_fusion_bn(self.image_fusion_conv(up)))
+                full = (li_fusion.Feature_Gather(img_fusion, xy) if self.sampler == "hip" else stock_feature_gather(img_fusion, xy))
             l_feat[0] = self.final_fusion_img_point(l_feat[0], full)
         return l_xyz[0], l_feat[0]

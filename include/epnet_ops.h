@@ -988,6 +988,35 @@ int epnet_adam_onecycle_step_scaled(int tensors, long long chunks, long long max
                                     double backoff_factor, long long growth_interval, double min_scale, void *workspace,
                                     size_t workspace_bytes, epnet_stream_t stream);
 
+/* LI-Fusion's image head evaluated at the points only (inference). In eval mode the end of the
+ * two-stream backbone -- cat_l(DeConv_l(F_l)) -> 1x1 convolution -> batch norm -> ReLU -> bilinear sampler
+ * (lib/net/pointnet2_msg.py:237-246) -- is pointwise per output pixel in front of the sampler (the deconvolutions have
+ * kernel == stride), so only the pixels under the four bilinear taps of each point are evaluated and the two full-resolution
+ * maps are never formed. For scene b, point n, output channel c:
+ *   out[b, c, n] = sum over the in-bounds taps, in the order nw, ne, sw, se, of weight_tap * relu(shift[c] + s_c(tap))
+ *   s_c(tap)     = sum_j in ascending order of wf[c, j] * d[j](tap), started from 0
+ *   d(tap)       = cat_l(d_l),  d_l[r] = sum_ci in ascending order of wd_l[Y % k_l, X % k_l, ci, r] * F_l[b, ci, Y / k_l, X / k_l]
+ * for the tap's pixel (Y, X); taps and weights are those of epnet_feature_gather. float32 in that order, no contraction, no
+ * float atomics: a tap's value depends on its pixel, its scene's maps and the weights alone.
+ *   levels: 1..8; chans[l] = C_l >= 1, kernels[l] = k_l in {1, 2, 4, 8, 16}, each dividing the largest; reduce[l] = R_l >= 1
+ *     (host arrays of `levels` ints); h, w multiples of the largest kernel
+ *   maps[l]: DEVICE pointer to F_l (b, C_l, h / k_l, w / k_l) fp32 contiguous; weights[l]: DEVICE pointer to wd_l packed
+ *     (k_l, k_l, C_l, R_l) (maps, weights: host arrays of `levels` pointers, read during the call)
+ *   wf (q, sum R) = the 1x1 weight times the batch-norm scale; shift (q) = everything constant per channel (batch-norm
+ *     shift, 1x1 bias, the 1x1 image of the deconvolution biases); xy (b, n, 2) normalised; out (b, q, n)
+ * A fixed number of launches (levels transposes + 5), no host synchronisation, no allocation; records into a HIP graph.
+ * Scratch: epnet_image_head_points_workspace_bytes, pure arithmetic (pixel-major copies of the maps, the per-tap values, the
+ * tap order and four tables of 256 bins; each part rounded up to 256 bytes; 0 outside the limits); the workspace must be
+ * 16-byte aligned. sum R <= 240, q <= 120, 4 * b * n < 2^31, b <= 65535, else EPNET_ELIMIT before any launch; an unsupported
+ * kernel size or map size, a NULL required pointer: EPNET_EINVAL; a short workspace: EPNET_ENOMEM; b == 0 or n == 0 returns
+ * EPNET_OK and writes nothing. PRECONDITION: neither out nor the workspace aliases an input. */
+size_t epnet_image_head_points_workspace_bytes(int b, int n, int h, int w, int levels, const int *chans, const int *kernels,
+                                               const int *reduce, int q);
+int epnet_image_head_points(int b, int n, int h, int w, int levels, const int *chans, const int *kernels, const int *reduce,
+                            const float *const *maps, const float *const *weights, int q, const float *wf, const float *shift,
+                            const float *xy, int align_corners, float *out, void *workspace, size_t workspace_bytes,
+                            epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
