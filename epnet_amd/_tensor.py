@@ -74,6 +74,15 @@ def need(t, numel, name):
         _bad(name, "has %d elements, the call needs %d" % (t.numel(), numel))
 
 
+def opt_ptr(t, name, dtype, count):
+    """device address of an optional tensor (None -> NULL)"""
+    if t is None:
+        return None
+    p = dev_ptr(t, name, dtype)
+    need(t, count, name)
+    return p
+
+
 class on_device_of:
     """Makes the tensor's device current for the launch and yields its current HIP stream.
 

@@ -27,6 +27,18 @@ int tuning(Knob k);
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 inline long long div_up64(long long a, long long b) { return (a + b - 1) / b; }
 
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// carves a workspace into 16-byte aligned parts: take(bytes) is the offset of the next part, `off` ends as the total
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off = align16(off + bytes);
+        return at;
+    }
+};
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 
 // number of set bits of `mask` strictly below this lane
@@ -89,7 +101,7 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
 }
 
 // float -> unsigned, order preserving; -0.0 and +0.0 share a key and so does every NaN (above +inf: torch.sort(descending)
-// puts a NaN first). The key rule of the second-stage detections (iou3d.hip) and of epnet_score_order (handover.hip).
+// puts a NaN first). The key rule of the second-stage detections (detections.hip) and of epnet_score_order (handover.hip).
 __device__ __forceinline__ unsigned ordered_key(float v) {
     if (v != v) return 0xffffffffu;
     if (v == 0.f) v = 0.f;

@@ -9,11 +9,7 @@
 #pragma once
 #include <math.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define EPNET_HD __host__ __device__ __forceinline__
-#else
-#define EPNET_HD inline
-#endif
+#include "cr_trig.h"  // EPNET_HD
 
 namespace epnet {
 

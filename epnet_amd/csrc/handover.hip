@@ -387,8 +387,6 @@ inline int launch_order(int b, int n, const float *scores, int64_t *order, hipSt
     return check_launch("score_order");
 }
 
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 }  // namespace handover
 }  // namespace epnet
 
@@ -421,8 +419,10 @@ extern "C" int epnet_score_order(int b, int n, const float *scores, int64_t *ord
 extern "C" size_t epnet_rpn_handover_workspace_bytes(int b, int n, int distance_based, int pre_nms_top_n, int post_nms_top_n) {
     if (b <= 0 || b > 32767 || n < 1 || n > handover::kOrderMaxN || pre_nms_top_n < 0 || post_nms_top_n < 0) return 0;
     const size_t rows = (size_t)b * (size_t)n;
-    return handover::align16(rows * 7 * sizeof(float)) + handover::align16(rows * sizeof(int64_t)) +
-           epnet_rpn_proposals_workspace_bytes(b, distance_based, pre_nms_top_n, post_nms_top_n);
+    Carver c;  // the decoded boxes, the score order, then the proposal layer's own workspace
+    c.take(rows * 7 * sizeof(float));
+    c.take(rows * sizeof(int64_t));
+    return c.off + epnet_rpn_proposals_workspace_bytes(b, distance_based, pre_nms_top_n, post_nms_top_n);
 }
 
 extern "C" int epnet_rpn_handover(int b, int n, int channels, const float *scores, const float *rpn_reg, const float *xyz,
@@ -443,10 +443,9 @@ extern "C" int epnet_rpn_handover(int b, int n, int channels, const float *score
     EPNET_REQUIRE(((uintptr_t)workspace & 15) == 0);
     const size_t rows = (size_t)b * (size_t)n;
     char *ws = (char *)workspace;
-    float *ws_proposals = (float *)ws;
-    ws += handover::align16(rows * 7 * sizeof(float));
-    int64_t *ws_order = (int64_t *)ws;
-    ws += handover::align16(rows * sizeof(int64_t));
+    Carver c;
+    float *ws_proposals = (float *)(ws + c.take(rows * 7 * sizeof(float)));
+    int64_t *ws_order = (int64_t *)(ws + c.take(rows * sizeof(int64_t)));
     if (!proposals) proposals = ws_proposals;
     if (!order) order = ws_order;
     hipStream_t s = (hipStream_t)stream;
@@ -456,6 +455,6 @@ extern "C" int epnet_rpn_handover(int b, int n, int channels, const float *score
     if (rc) return rc;
     rc = handover::launch_order(b, n, scores, order, s);
     if (rc) return rc;
-    return epnet_rpn_proposals(b, n, proposals, scores, order, distance_based, pre_nms_top_n, post_nms_top_n, nms_thresh, rotated, ws,
-                               workspace_bytes - (size_t)(ws - (char *)workspace), ret_bbox3d, ret_scores, ret_count, stream);
+    return epnet_rpn_proposals(b, n, proposals, scores, order, distance_based, pre_nms_top_n, post_nms_top_n, nms_thresh, rotated,
+                               ws + c.off, workspace_bytes - c.off, ret_bbox3d, ret_scores, ret_count, stream);
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "cr_trig.h"
 
 namespace epnet {
 
@@ -81,8 +82,7 @@ static inline BoxTerms box_terms(const float *b) {
     t.hh = b[3] * 0.5f;
     t.hw = b[4] * 0.5f;
     t.hl = b[5] * 0.5f;
-    t.cosa = (float)cos((double)b[6]);
-    t.sina = (float)sin((double)b[6]);
+    cr_cossinf(b[6], t.cosa, t.sina);
     return t;
 }
 

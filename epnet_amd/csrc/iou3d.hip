@@ -3,178 +3,22 @@
 // Replaces lib/utils/iou3d/src/iou3d_kernel.cu (box_overlap :108-212, iou_bev :214-221,
 // boxes_overlap_kernel :223-234, boxes_iou_bev_kernel :236-248, nms_kernel :250-292, iou_normal
 // :295-303, nms_normal_kernel :306-348) and the host half of lib/utils/iou3d/src/iou3d.cpp:73-170.
+// The pair geometry itself (box_overlap, iou_bev, iou_normal, iou3d_pair) is boxgeom.h.
 //
 // Differences in structure, not in results:
-//   * box_overlap evaluates each polygon vertex's atan2 once and bubble-sorts on the stored
-//     angles (the reference recomputes two atan2 per comparison, :104-106, :188-196): the same
-//     deterministic function of the same arguments, hence the same swaps in the same order;
 //   * the NMS bit-mask is computed for the upper triangle only, one wave per (row, 64-column tile) -- the host sweep
 //     (iou3d.cpp:111-114) never reads a word left of the diagonal;
 //   * the greedy sweep runs on the device (one workgroup): no cudaMalloc / 5 MB device->host
 //     copy / host loop per call (iou3d.cpp:87-116).
 // Trigonometry: correctly rounded float cos/sin/atan2 via the double-precision functions, the
-// same definition the oracle uses (DESIGN.md "Parity definition").
+// same definition the oracle uses (DESIGN.md "Parity definition", cr_trig.h).
 #include <math.h>
 
+#include "boxgeom.h"
 #include "common.h"
-#include "dpp.h"
+#include "nms.h"
 
 namespace epnet {
-
-constexpr float kIouEps = 1e-8f;  // iou3d_kernel.cu:13
-
-__device__ __forceinline__ float cr_cosf(float x) { return (float)cos((double)x); }
-__device__ __forceinline__ float cr_sinf(float x) { return (float)sin((double)x); }
-__device__ __forceinline__ float cr_atan2f(float y, float x) { return (float)atan2((double)y, (double)x); }
-
-struct P2 {
-    float x, y;
-};
-
-__device__ __forceinline__ float cross3(P2 p1, P2 p2, P2 p0) {  // :38-40
-    return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
-}
-
-__device__ __forceinline__ bool rect_cross(P2 p1, P2 p2, P2 q1, P2 q2) {  // :42-48
-    return fminf(p1.x, p2.x) <= fmaxf(q1.x, q2.x) && fminf(q1.x, q2.x) <= fmaxf(p1.x, p2.x) &&
-           fminf(p1.y, p2.y) <= fmaxf(q1.y, q2.y) && fminf(q1.y, q2.y) <= fmaxf(p1.y, p2.y);
-}
-
-// check_in_box2d (:50-65) with the box's cos(-ry), sin(-ry) passed in
-__device__ __forceinline__ bool in_box2d(const float *box, float ncos, float nsin, P2 p) {
-    const float MARGIN = 1e-5f;
-    const float center_x = (box[0] + box[2]) / 2;
-    const float center_y = (box[1] + box[3]) / 2;
-    const float rot_x = (p.x - center_x) * ncos + (p.y - center_y) * nsin + center_x;
-    const float rot_y = -(p.x - center_x) * nsin + (p.y - center_y) * ncos + center_y;
-    return rot_x > box[0] - MARGIN && rot_x < box[2] + MARGIN && rot_y > box[1] - MARGIN && rot_y < box[3] + MARGIN;
-}
-
-__device__ __forceinline__ bool seg_intersection(P2 p1, P2 p0, P2 q1, P2 q0, P2 &ans) {  // :67-96
-    if (!rect_cross(p0, p1, q0, q1)) return false;
-    const float s1 = cross3(q0, p1, p0);
-    const float s2 = cross3(p1, q1, p0);
-    const float s3 = cross3(p0, q1, q0);
-    const float s4 = cross3(q1, p1, q0);
-    if (!(s1 * s2 > 0 && s3 * s4 > 0)) return false;
-    const float s5 = cross3(q1, p1, p0);
-    if (fabsf(s5 - s1) > kIouEps) {
-        ans.x = (s5 * q0.x - s1 * q1.x) / (s5 - s1);
-        ans.y = (s5 * q0.y - s1 * q1.y) / (s5 - s1);
-    } else {
-        const float a0 = p0.y - p1.y, b0 = p1.x - p0.x, c0 = p0.x * p1.y - p1.x * p0.y;
-        const float a1 = q0.y - q1.y, b1 = q1.x - q0.x, c1 = q0.x * q1.y - q1.x * q0.y;
-        const float D = a0 * b1 - a1 * b0;
-        ans.x = (b0 * c1 - b1 * c0) / D;
-        ans.y = (a1 * c0 - a0 * c1) / D;
-    }
-    return true;
-}
-
-__device__ __forceinline__ void rot_center(P2 center, float c, float s, P2 &p) {  // :98-102
-    const float nx = (p.x - center.x) * c + (p.y - center.y) * s + center.x;
-    const float ny = -(p.x - center.x) * s + (p.y - center.y) * c + center.y;
-    p.x = nx;
-    p.y = ny;
-}
-
-// per-box trigonometry: cos/sin of +ry (corner rotation) and of -ry (point-in-box test)
-struct BoxTrig {
-    float c, s, nc, ns;
-};
-
-__device__ __forceinline__ BoxTrig box_trig(float ry) {
-    BoxTrig t;
-    t.c = cr_cosf(ry);
-    t.s = cr_sinf(ry);
-    t.nc = cr_cosf(-ry);
-    t.ns = cr_sinf(-ry);
-    return t;
-}
-
-__device__ float box_overlap(const float *box_a, const float *box_b, BoxTrig ta, BoxTrig tb) {  // :108-212
-    const float a_x1 = box_a[0], a_y1 = box_a[1], a_x2 = box_a[2], a_y2 = box_a[3];
-    const float b_x1 = box_b[0], b_y1 = box_b[1], b_x2 = box_b[2], b_y2 = box_b[3];
-    const P2 center_a = {(a_x1 + a_x2) / 2, (a_y1 + a_y2) / 2};
-    const P2 center_b = {(b_x1 + b_x2) / 2, (b_y1 + b_y2) / 2};
-    P2 ac[5] = {{a_x1, a_y1}, {a_x2, a_y1}, {a_x2, a_y2}, {a_x1, a_y2}, {0.f, 0.f}};
-    P2 bc[5] = {{b_x1, b_y1}, {b_x2, b_y1}, {b_x2, b_y2}, {b_x1, b_y2}, {0.f, 0.f}};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        rot_center(center_a, ta.c, ta.s, ac[k]);
-        rot_center(center_b, tb.c, tb.s, bc[k]);
-    }
-    ac[4] = ac[0];
-    bc[4] = bc[0];
-
-    P2 cp[24];  // the reference has 16 slots; two rectangles cannot produce more than 16 entries
-    float ang[24];
-    P2 pc = {0.f, 0.f};
-    int cnt = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            P2 r;
-            if (seg_intersection(ac[i + 1], ac[i], bc[j + 1], bc[j], r)) {
-                pc.x = pc.x + r.x;
-                pc.y = pc.y + r.y;
-                cp[cnt++] = r;
-            }
-        }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (in_box2d(box_a, ta.nc, ta.ns, bc[k])) {
-            pc.x = pc.x + bc[k].x;
-            pc.y = pc.y + bc[k].y;
-            cp[cnt++] = bc[k];
-        }
-        if (in_box2d(box_b, tb.nc, tb.ns, ac[k])) {
-            pc.x = pc.x + ac[k].x;
-            pc.y = pc.y + ac[k].y;
-            cp[cnt++] = ac[k];
-        }
-    }
-    pc.x /= cnt;
-    pc.y /= cnt;
-
-    for (int i = 0; i < cnt; ++i) ang[i] = cr_atan2f(cp[i].y - pc.y, cp[i].x - pc.x);
-    for (int j = 0; j < cnt - 1; ++j)
-        for (int i = 0; i < cnt - j - 1; ++i)
-            if (ang[i] > ang[i + 1]) {
-                const P2 tp = cp[i];
-                cp[i] = cp[i + 1];
-                cp[i + 1] = tp;
-                const float ta_ = ang[i];
-                ang[i] = ang[i + 1];
-                ang[i + 1] = ta_;
-            }
-
-    float area = 0.f;
-    for (int k = 0; k < cnt - 1; ++k) {
-        const float ax = cp[k].x - cp[0].x, ay = cp[k].y - cp[0].y;
-        const float bx = cp[k + 1].x - cp[0].x, by = cp[k + 1].y - cp[0].y;
-        area += ax * by - ay * bx;
-    }
-    return fabsf(area) / 2.0f;
-}
-
-__device__ __forceinline__ float iou_bev(const float *box_a, const float *box_b, BoxTrig ta, BoxTrig tb) {  // :214-221
-    const float sa = (box_a[2] - box_a[0]) * (box_a[3] - box_a[1]);
-    const float sb = (box_b[2] - box_b[0]) * (box_b[3] - box_b[1]);
-    const float s_overlap = box_overlap(box_a, box_b, ta, tb);
-    return s_overlap / fmaxf(sa + sb - s_overlap, kIouEps);
-}
-
-__device__ __forceinline__ float iou_normal(const float *a, const float *b) {  // :295-303
-    const float left = fmaxf(a[0], b[0]), right = fminf(a[2], b[2]);
-    const float top = fmaxf(a[1], b[1]), bottom = fminf(a[3], b[3]);
-    const float width = fmaxf(right - left, 0.f), height = fmaxf(bottom - top, 0.f);
-    const float interS = width * height;
-    const float Sa = (a[2] - a[0]) * (a[3] - a[1]);
-    const float Sb = (b[2] - b[0]) * (b[3] - b[1]);
-    return interS / fmaxf(Sa + Sb - interS, kIouEps);
-}
 
 // one thread per (a, b) pair; 64 b's x 4 a's per workgroup, the b boxes' trig staged in LDS
 template <bool IOU>
@@ -193,33 +37,7 @@ __global__ __launch_bounds__(256) void pairwise_bev_kernel(int num_a, const floa
     ans[(size_t)a_idx * num_b + b_idx] = IOU ? iou_bev(ba, bb, ta, tb) : box_overlap(ba, bb, ta, tb);
 }
 
-// ---- fused 3-D IoU (boxes_iou3d_gpu of lib/utils/iou3d/iou3d_utils.py:21-53 in ONE launch) -------------
-// The reference builds the BEV boxes (kitti_utils.boxes3d_to_bev_torch :137-150), calls the overlap kernel and
-// finishes with ~10 small torch kernels (height overlap, volumes, clamp, divide). Every step is an fp32
-// elementwise op, reproduced here in the same order, so the values equal that composition.
-// boxes: (.,7) [x, y, z, h, w, l, ry], y = bottom centre, camera coordinates.
-__device__ __forceinline__ void bev_of(const float *b7, float *bev) {
-    const float half_l = b7[5] / 2, half_w = b7[4] / 2;
-    bev[0] = b7[0] - half_l;
-    bev[1] = b7[2] - half_w;
-    bev[2] = b7[0] + half_l;
-    bev[3] = b7[2] + half_w;
-    bev[4] = b7[6];
-}
-
-__device__ __forceinline__ float iou3d_pair(const float *a7, const float *b7) {
-    float ba[5], bb[5];
-    bev_of(a7, ba);
-    bev_of(b7, bb);
-    const float overlaps_bev = box_overlap(ba, bb, box_trig(ba[4]), box_trig(bb[4]));
-    const float a_min = a7[1] - a7[3], a_max = a7[1], b_min = b7[1] - b7[3], b_max = b7[1];
-    const float max_of_min = fmaxf(a_min, b_min), min_of_max = fminf(a_max, b_max);
-    const float overlaps_h = fmaxf(min_of_max - max_of_min, 0.f);
-    const float overlaps_3d = overlaps_bev * overlaps_h;
-    const float vol_a = a7[3] * a7[4] * a7[5], vol_b = b7[3] * b7[4] * b7[5];
-    return overlaps_3d / fmaxf(vol_a + vol_b - overlaps_3d, 1e-7f);
-}
-
+// the fused 3-D IoU (iou3d_pair, boxgeom.h) of every (a, b) pair, and of pair i of two equally long lists
 __global__ __launch_bounds__(256) void iou3d_matrix_kernel(int num_a, const float *__restrict__ boxes_a, int num_b,
                                                            const float *__restrict__ boxes_b, float *__restrict__ ans) {
     const int b_idx = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -247,126 +65,12 @@ __global__ __launch_bounds__(256) void iou3d_pairs_kernel(int k, const float *__
     ans[i] = iou3d_pair(a7, b7);
 }
 
-// ---- ROI augmentation by noise (lib/rpn/proposal_target_layer.py:220-247, aug_roi_by_noise_torch) ----------
-// The reference walks the sampled ROIs one by one on the host: per ROI up to aug_times tries, each a host coin
-// (np.random.rand() < 0.2 keeps the ROI as it is), a noisy box built by five small torch kernels
-// (random_aug_box3d :250-275), a single-pair boxes_iou3d_gpu (another ~15 launches) and a device->host read of the
-// IoU for the loop condition -- up to 640 such round trips per scene. Here the random draws of ALL tries are
-// the caller's tables (drawn on the device with no sync), every (ROI, try) IoU is evaluated by its own lane, and
-// the first try whose IoU ends the reference's loop (`not (iou < pos_thresh)`) is found with one ballot:
-// the same boxes and IoUs as the loop fed with draw [k][cnt] at try cnt of ROI k.
-//   keep_draw (k, aug_times) u8: 1 = "keep the original ROI" (:232-234)
-//   noise (k, aug_times, 7) f32: pos_shift[3], hwl_scale[3], angle_rot -- aug = [xyz + shift, hwl * scale, ry + rot] (:259,274)
-__device__ __forceinline__ void aug_box_of(const float *roi, const float *nz, bool keep, float *aug) {
-#pragma unroll
-    for (int j = 0; j < 7; ++j) aug[j] = roi[j];
-    if (!keep) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) aug[j] = roi[j] + nz[j];
-#pragma unroll
-        for (int j = 3; j < 6; ++j) aug[j] = roi[j] * nz[j];
-        aug[6] = roi[6] + nz[6];
-    }
-}
-
-// TP = tries per ROI rounded up to a power of two (<= 64): 64 / TP ROIs per wave, lane = (roi, try)
-__global__ __launch_bounds__(256) void aug_roi_wave_kernel(int k, int aug_times, int tp, float pos_thresh,
-                                                           float *__restrict__ rois, const float *__restrict__ gts,
-                                                           const float *__restrict__ iou_src, const int *__restrict__ tries,
-                                                           const unsigned char *__restrict__ keep_draw,
-                                                           const float *__restrict__ noise, float *__restrict__ iou_out) {
-    const int lane = lane_id();
-    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int per_wave = 64 / tp;
-    const int grp = lane / tp, t = lane - grp * tp;
-    const int r = wave * per_wave + grp;
-    const int n_try = r < k ? (tries ? min(max(tries[r], 0), aug_times) : aug_times) : 0;
-    const bool active = t < n_try;
-    float roi[7], gt[7], aug[7], nz[7];
-    bool keep = true;
-    float iou = 0.f;
-    if (active) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            roi[j] = rois[(size_t)r * 7 + j];
-            gt[j] = gts[(size_t)r * 7 + j];
-            nz[j] = noise[((size_t)r * aug_times + t) * 7 + j];
-        }
-        keep = keep_draw[(size_t)r * aug_times + t] != 0;
-        aug_box_of(roi, nz, keep, aug);
-        iou = iou3d_pair(aug, gt);
-    }
-    // the loop runs try t+1 only while temp_iou < pos_thresh (:231): a try ends it when that comparison is false
-    const unsigned long long ends = __ballot(active && !(iou < pos_thresh));
-    const unsigned long long group_mask = (tp == 64 ? ~0ull : ((1ull << tp) - 1)) << (grp * tp);
-    const unsigned long long mine = ends & group_mask;
-    const int last = mine ? (__builtin_ctzll(mine) - grp * tp) : (n_try - 1);
-    __syncthreads();  // every lane has read its ROI before the winners overwrite rows (waves of a block share no ROI,
-                      // lanes of a wave are in lockstep; the barrier only orders the stores after the loads)
-    if (active && t == last) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) rois[(size_t)r * 7 + j] = aug[j];
-        iou_out[r] = keep ? iou_src[r] : iou;  // :243-246
-    }
-    if (r < k && n_try == 0 && t == 0) iou_out[r] = iou_src[r];  // no try ran (cnt == 0, :243): box untouched
-}
-
-// any number of tries: one thread walks the loop of one ROI
-__global__ __launch_bounds__(64) void aug_roi_serial_kernel(int k, int aug_times, float pos_thresh, float *__restrict__ rois,
-                                                            const float *__restrict__ gts, const float *__restrict__ iou_src,
-                                                            const int *__restrict__ tries,
-                                                            const unsigned char *__restrict__ keep_draw,
-                                                            const float *__restrict__ noise, float *__restrict__ iou_out) {
-    const int r = blockIdx.x * 64 + threadIdx.x;
-    if (r >= k) return;
-    const int n_try = tries ? min(max(tries[r], 0), aug_times) : aug_times;
-    float roi[7], gt[7], aug[7], nz[7];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-        roi[j] = rois[(size_t)r * 7 + j];
-        gt[j] = gts[(size_t)r * 7 + j];
-        aug[j] = roi[j];
-    }
-    float temp_iou = 0.f;
-    int cnt = 0;
-    bool keep = true;
-    while (temp_iou < pos_thresh && cnt < n_try) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) nz[j] = noise[((size_t)r * aug_times + cnt) * 7 + j];
-        keep = keep_draw[(size_t)r * aug_times + cnt] != 0;
-        aug_box_of(roi, nz, keep, aug);
-        temp_iou = iou3d_pair(aug, gt);
-        ++cnt;
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) rois[(size_t)r * 7 + j] = aug[j];
-    iou_out[r] = (cnt == 0 || keep) ? iou_src[r] : temp_iou;
-}
-
-// per-box trigonometry, once per box instead of once per pair
+// ---- rotated NMS mask (nms_kernel, iou3d_kernel.cu:250-292) ------------------------------------------------------
 // Batched form of all three NMS kernels: group = blockIdx.z (y for the 1-D ones) with `cap` boxes of room per group and
 // the group's box count read from device memory (counts[group], clamped to cap) -- a caller whose counts are produced
 // on the device (the proposal layer) never has to read them back. counts == NULL: one group of boxes_num boxes.
-__global__ __launch_bounds__(256) void box_trig_kernel(int n, const int *__restrict__ counts, int cap,
-                                                       const float *__restrict__ boxes, BoxTrig *__restrict__ trig) {
-    const int grp = blockIdx.y;
-    if (counts) n = min(counts[grp], cap);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) trig[(size_t)grp * cap + i] = box_trig(boxes[((size_t)grp * cap + i) * 5 + 4]);
-}
 
-// ---- rotated NMS mask (nms_kernel, iou3d_kernel.cu:250-292) ------------------------------------------------------
-// Everything of a pair's overlap that depends on ONE box is computed once per box: the rotated corners (same expressions
-// as box_overlap), their axis-aligned hull, cos / sin of -ry for the point-in-box test, the box area.
-struct BoxRot {
-    float x1, y1, x2, y2;      // the BEV box itself
-    float nc, ns;              // cos(-ry), sin(-ry): check_in_box2d (:50-65)
-    float cx[4], cy[4];        // corners after rotate_around_center (:98-102, :141-146)
-    float minx, maxx, miny, maxy;
-    float area, pad;
-};
-static_assert(sizeof(BoxRot) == 80, "BoxRot layout");
-
+// per-box record (BoxRot, boxgeom.h), once per box instead of once per pair
 __global__ __launch_bounds__(256) void box_rot_kernel(int n, const int *__restrict__ counts, int cap,
                                                       const float *__restrict__ boxes, BoxRot *__restrict__ rot) {
     const int grp = blockIdx.y;
@@ -528,13 +232,11 @@ __global__ __launch_bounds__(kRotThreads) void nms_mask_rot_kernel(int boxes_num
     }
 }
 
-// suppression bit-mask, upper triangle only: one WAVE per (row, 64-column tile) -- each lane owns one
-// pair and the 64-bit mask word is the wave's ballot (the reference gives a thread a whole row of 64
+// axis-aligned suppression bit-mask (nms_normal_kernel :306-348), upper triangle only: one WAVE per (row, 64-column tile)
+// -- each lane owns one pair and the 64-bit mask word is the wave's ballot (the reference gives a thread a whole row of 64
 // pairs, :281-290)
-template <bool ROTATED>
 __global__ __launch_bounds__(256) void nms_mask_kernel(int boxes_num, const int *__restrict__ counts, int cap, float thresh,
-                                                       const float *__restrict__ boxes, const BoxTrig *__restrict__ trig,
-                                                       unsigned long long *__restrict__ mask) {
+                                                       const float *__restrict__ boxes, unsigned long long *__restrict__ mask) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int col_blk = blockIdx.y;
@@ -542,7 +244,6 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(int boxes_num, const int 
     if (counts) boxes_num = min(counts[grp], cap);
     const int stride = counts ? (cap + 63) / 64 : (boxes_num + 63) / 64;  // mask words per row
     boxes += (size_t)grp * cap * 5;
-    trig += (size_t)grp * cap;
     mask += (size_t)grp * cap * stride;
     if (row >= boxes_num || col_blk < (row >> 6) || col_blk * 64 >= boxes_num) return;  // wave-uniform: tiles left of the diagonal are never read
     const int col = col_blk * 64 + lane;
@@ -554,8 +255,7 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(int boxes_num, const int 
             cb[i] = boxes[row * 5 + i];
             ob[i] = boxes[col * 5 + i];
         }
-        const float v = ROTATED ? iou_bev(cb, ob, trig[row], trig[col]) : iou_normal(cb, ob);
-        over = v > thresh;
+        over = iou_normal(cb, ob) > thresh;
     }
     const unsigned long long bits = __ballot(over);
     if (lane == 0) mask[(size_t)row * stride + col_blk] = bits;
@@ -642,604 +342,27 @@ __global__ __launch_bounds__(kSweepThreads) void nms_sweep_kernel(int boxes_num,
     if (threadIdx.x == 0) *num_keep = kept_total;
 }
 
-template <bool ROTATED>
-static int nms_impl(const float *boxes, int boxes_num, float thresh, void *workspace, size_t workspace_bytes,
-                    int64_t *keep, int *num_keep, hipStream_t s) {
-    if (boxes_num < 0) return EPNET_EINVAL;
-    if (!num_keep) return EPNET_EINVAL;
-    if (boxes_num == 0) {
-        hipError_t e = hipMemsetAsync(num_keep, 0, sizeof(int), s);
-        return e == hipSuccess ? EPNET_OK : record_hip_error(e, "nms memset");
-    }
-    if (!(boxes && keep && workspace)) return EPNET_EINVAL;
-    if (workspace_bytes < epnet_nms_workspace_bytes(boxes_num)) return EPNET_ENOMEM;
-    const int col_blocks = (boxes_num + 63) / 64;
-    if (col_blocks > 65535 || (size_t)col_blocks * 8 > 60 * 1024) return EPNET_ELIMIT;
-    unsigned long long *mask = (unsigned long long *)workspace;
-    BoxRot *rot = (BoxRot *)(mask + (size_t)boxes_num * col_blocks);
-    if (ROTATED) {
-        hipLaunchKernelGGL(box_rot_kernel, dim3(div_up(boxes_num, 256)), dim3(256), 0, s, boxes_num, (const int *)nullptr, boxes_num,
-                           boxes, rot);
-        int rc0 = check_launch("nms_rot");
-        if (rc0) return rc0;
-        hipLaunchKernelGGL(nms_mask_rot_kernel, dim3(col_blocks, col_blocks), dim3(kRotThreads), 0, s, boxes_num, (const int *)nullptr,
-                           boxes_num, thresh, rot, mask);
-    } else {
-        hipLaunchKernelGGL(nms_mask_kernel<false>, dim3(div_up(boxes_num, 4), col_blocks), dim3(256), 0, s, boxes_num,
-                           (const int *)nullptr, boxes_num, thresh, boxes, (const BoxTrig *)nullptr, mask);
-    }
-    int rc = check_launch("nms_mask");
-    if (rc) return rc;
-    hipLaunchKernelGGL(nms_sweep_kernel, dim3(1), dim3(kSweepThreads), (size_t)col_blocks * 8, s, boxes_num, (const int *)nullptr,
-                       boxes_num, mask, (long long *)keep, num_keep);
-    return check_launch("nms_sweep");
-}
-
-// `groups` independent NMS problems of at most `cap` boxes each, counts on the device (see the kernels)
-static int nms_groups(bool rotated, int groups, int cap, const int *counts, const float *boxes, float thresh, BoxRot *rot,
-                      unsigned long long *mask, long long *keep, int *num_keep, hipStream_t s) {
+// the one NMS launch sequence (nms.h): per-box records + rotated mask, or the axis-aligned mask; then the sweep
+int nms_groups(bool rotated, int groups, int cap, const int *counts, const float *boxes, float thresh, BoxRot *rot,
+               unsigned long long *mask, long long *keep, int *num_keep, hipStream_t s) {
     const int col_blocks = (cap + 63) / 64;
+    const int boxes_num = counts ? 0 : cap;  // the kernels' scalar count, read only without counts
     if (col_blocks > 65535 || groups > 65535 || (size_t)col_blocks * 8 > 60 * 1024) return EPNET_ELIMIT;
     if (rotated) {
-        hipLaunchKernelGGL(box_rot_kernel, dim3(div_up(cap, 256), groups), dim3(256), 0, s, 0, counts, cap, boxes, rot);
+        hipLaunchKernelGGL(box_rot_kernel, dim3(div_up(cap, 256), groups), dim3(256), 0, s, boxes_num, counts, cap, boxes, rot);
         int rc0 = check_launch("nms_rot");
         if (rc0) return rc0;
-        hipLaunchKernelGGL(nms_mask_rot_kernel, dim3(col_blocks, col_blocks, groups), dim3(kRotThreads), 0, s, 0, counts, cap, thresh,
-                           rot, mask);
+        hipLaunchKernelGGL(nms_mask_rot_kernel, dim3(col_blocks, col_blocks, groups), dim3(kRotThreads), 0, s, boxes_num, counts, cap,
+                           thresh, rot, mask);
     } else {
-        hipLaunchKernelGGL(nms_mask_kernel<false>, dim3(div_up(cap, 4), col_blocks, groups), dim3(256), 0, s, 0, counts, cap, thresh,
-                           boxes, (const BoxTrig *)nullptr, mask);
+        hipLaunchKernelGGL(nms_mask_kernel, dim3(div_up(cap, 4), col_blocks, groups), dim3(256), 0, s, boxes_num, counts, cap, thresh,
+                           boxes, mask);
     }
     int rc = check_launch("nms_mask");
     if (rc) return rc;
-    hipLaunchKernelGGL(nms_sweep_kernel, dim3(groups), dim3(kSweepThreads), (size_t)col_blocks * 8, s, 0, counts, cap, mask, keep,
-                       num_keep);
+    hipLaunchKernelGGL(nms_sweep_kernel, dim3(groups), dim3(kSweepThreads), (size_t)col_blocks * 8, s, boxes_num, counts, cap, mask,
+                       keep, num_keep);
     return check_launch("nms_sweep");
-}
-
-// ---- proposal layer (lib/rpn/proposal_layer.py:15-142) ---------------------------------------
-// The reference walks the scenes on the host: boolean-mask indexing by distance bin (a sync each), top-K slices, NMS (mask
-// to the host, host sweep), more slices, torch.cat, copy into the zero-padded result -- about ten host syncs per scene.
-// Here: (1) one workgroup per scene walks the score-sorted order and compacts the members of each distance bin, in order,
-// up to the bin's pre-NMS budget, and writes their BEV boxes (kitti_utils.boxes3d_to_bev_torch :137-150); (2) the NMS of
-// all (scene, bin) groups runs as one batched mask + sweep with the group sizes read from device memory; (3) one kernel
-// gathers the first post-NMS survivors of bin 0, then of bin 1, into the zero-padded (b, post, 7) / (b, post) results.
-// No value leaves the device. bins == 1 is score_based_proposal (:121-142): one bin that takes every box.
-constexpr int kBinThreads = 1024;
-
-__device__ __forceinline__ int bin_of(float z, int bins) {  // nms_range_list = [0, 40, 80] (:65, :77-80)
-    if (bins == 1) return 0;
-    if (z > 0.f && z <= 40.f) return 0;
-    if (z > 40.f && z <= 80.f) return 1;
-    return -1;
-}
-
-// sel (b, 2, tot): positions IN THE SORTED ORDER of the members of each bin; counts (b*2): members kept for the NMS
-__global__ __launch_bounds__(kBinThreads) void proposal_bin_kernel(int n, int bins, int pre0, int pre1, int cap,
-                                                                   const float *__restrict__ proposals,
-                                                                   const long long *__restrict__ order, int *__restrict__ sel,
-                                                                   int *__restrict__ counts, float *__restrict__ bev) {
-    __shared__ int wave_cnt[2][kBinThreads / 64];
-    __shared__ int base[2];
-    const int scene = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6;
-    const int tot = pre0 + pre1;
-    proposals += (size_t)scene * n * 7;
-    order += (size_t)scene * n;
-    int *sel0 = sel + (size_t)scene * 2 * tot, *sel1 = sel0 + tot;
-    if (threadIdx.x < 2) base[threadIdx.x] = 0;
-    __syncthreads();
-    for (int start = 0; start < n; start += kBinThreads) {
-        const int i = start + threadIdx.x;
-        int bin = -1;
-        if (i < n) bin = bin_of(proposals[(size_t)order[i] * 7 + 2], bins);
-        const unsigned long long m0 = __ballot(bin == 0), m1 = __ballot(bin == 1);
-        if (lane == 0) {
-            wave_cnt[0][wave] = __popcll(m0);
-            wave_cnt[1][wave] = __popcll(m1);
-        }
-        __syncthreads();
-        int before0 = base[0], before1 = base[1];
-        for (int w = 0; w < wave; ++w) {
-            before0 += wave_cnt[0][w];
-            before1 += wave_cnt[1][w];
-        }
-        // bin 0 keeps pre0 + pre1 members: the tail serves bin 1 when that area holds no box at all (:92-100)
-        if (bin == 0) {
-            const int pos = before0 + popc_below(m0);
-            if (pos < tot) sel0[pos] = i;
-        } else if (bin == 1) {
-            const int pos = before1 + popc_below(m1);
-            if (pos < pre1) sel1[pos] = i;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int t0 = 0, t1 = 0;
-            for (int w = 0; w < kBinThreads / 64; ++w) {
-                t0 += wave_cnt[0][w];
-                t1 += wave_cnt[1][w];
-            }
-            base[0] += t0;
-            base[1] += t1;
-        }
-        __syncthreads();
-    }
-    const int c0 = base[0], c1 = base[1];
-    const int n0 = min(c0, pre0);
-    int n1 = min(c1, pre1);
-    if (bins == 2 && c1 == 0) {  // "this area doesn't have any points, so use rois of first area" (:92-100)
-        n1 = max(min(c0, tot) - pre0, 0);
-        for (int j = threadIdx.x; j < n1; j += kBinThreads) sel1[j] = sel0[pre0 + j];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        counts[scene * 2] = n0;
-        counts[scene * 2 + 1] = bins == 2 ? n1 : 0;
-    }
-    // BEV boxes of the members, in order: [x - l/2, z - w/2, x + l/2, z + w/2, ry]
-    for (int bin = 0; bin < bins; ++bin) {
-        const int cnt = bin ? n1 : n0;
-        const int *src = bin ? sel1 : sel0;
-        float *dst = bev + ((size_t)scene * 2 + bin) * cap * 5;
-        for (int j = threadIdx.x; j < cnt; j += kBinThreads) {
-            const float *p = proposals + (size_t)order[src[j]] * 7;
-            const float half_l = p[5] / 2, half_w = p[4] / 2;
-            dst[j * 5 + 0] = p[0] - half_l;
-            dst[j * 5 + 1] = p[2] - half_w;
-            dst[j * 5 + 2] = p[0] + half_l;
-            dst[j * 5 + 3] = p[2] + half_w;
-            dst[j * 5 + 4] = p[6];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void proposal_emit_kernel(int n, int pre0, int pre1, int cap, int post0, int post1,
-                                                            const float *__restrict__ proposals, const float *__restrict__ scores,
-                                                            const long long *__restrict__ order, const int *__restrict__ sel,
-                                                            const long long *__restrict__ keep, const int *__restrict__ num_keep,
-                                                            float *__restrict__ ret_bbox3d, float *__restrict__ ret_scores,
-                                                            int *__restrict__ ret_count) {
-    const int scene = blockIdx.x;
-    const int tot = pre0 + pre1, post = post0 + post1;
-    const int k0 = min(num_keep[scene * 2], post0), k1 = min(num_keep[scene * 2 + 1], post1);
-    if (threadIdx.x == 0 && ret_count) ret_count[scene] = k0 + k1;
-    for (int j = threadIdx.x; j < post; j += 256) {
-        float row[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float sc = 0.f;
-        if (j < k0 + k1) {  // the kept boxes of bin 0, then those of bin 1 (torch.cat, :117-118)
-            const int bin = j < k0 ? 0 : 1, pos = j < k0 ? j : j - k0;
-            const int member = (int)keep[((size_t)scene * 2 + bin) * cap + pos];
-            const long long src = order[(size_t)scene * n + sel[((size_t)scene * 2 + bin) * tot + member]];
-#pragma unroll
-            for (int q = 0; q < 7; ++q) row[q] = proposals[((size_t)scene * n + src) * 7 + q];
-            sc = scores[(size_t)scene * n + src];
-        }
-#pragma unroll
-        for (int q = 0; q < 7; ++q) ret_bbox3d[((size_t)scene * post + j) * 7 + q] = row[q];
-        ret_scores[(size_t)scene * post + j] = sc;
-    }
-}
-
-// ---- second-stage detections (tools/eval_rcnn.py:663-683) -----------------------------------------------------------------
-// The reference walks the scenes on the host: `inds.sum() == 0` (a sync), boolean-mask indexing (a sync), a sort, nms_gpu (mask
-// to the host, host sweep), more indexing. Here: (1) one workgroup per scene thresholds the scores, ranks the candidates --
-// descending score, equal scores by ascending index -- and writes their BEV boxes in rank order; (2) the batched NMS of the
-// proposal layer with the candidate counts read from device memory; (3) one kernel gathers the kept boxes and raw scores
-// into the zero-padded results. No value leaves the device.
-constexpr int kDetThreads = 1024;
-constexpr int kDetMaxM = 4096;
-
-// ordered_key (common.h): float -> unsigned, order preserving; it fixes the order of the candidates below
-
-// sel (b, m): ROI index of the candidate at each rank; counts (b): candidates; bev (b, m, 5) in rank order
-__global__ __launch_bounds__(kDetThreads) void det_select_kernel(int m, float score_thresh, const float *__restrict__ boxes3d,
-                                                                 const float *__restrict__ raw_scores,
-                                                                 const float *__restrict__ norm_scores, int *__restrict__ sel,
-                                                                 int *__restrict__ counts, float *__restrict__ bev) {
-    __shared__ unsigned long long keys[kDetMaxM];
-    __shared__ int s_count;
-    const int scene = blockIdx.x, lane = lane_id();
-    boxes3d += (size_t)scene * m * 7;
-    raw_scores += (size_t)scene * m;
-    norm_scores += (size_t)scene * m;
-    sel += (size_t)scene * m;
-    bev += (size_t)scene * m * 5;
-    if (threadIdx.x == 0) s_count = 0;
-    __syncthreads();
-    // candidates into LDS in any order: the key (score, then the LOWER index first) is unique, so the rank below does not
-    // depend on where a key sits. Every wave runs the same number of rounds (ballot over whole waves).
-    for (int start = 0; start < m; start += kDetThreads) {
-        const int i = start + threadIdx.x;
-        const int ic = min(i, m - 1);
-        const float norm = norm_scores[ic], raw = raw_scores[ic];
-        const bool cand = i < m && norm > score_thresh;
-        const unsigned long long mask = __ballot(cand);
-        if (mask) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&s_count, (int)__popcll(mask));
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (cand) keys[base + popc_below(mask)] = ((unsigned long long)ordered_key(raw) << 32) | (unsigned)(~(unsigned)i);
-        }
-    }
-    __syncthreads();
-    const int c = s_count;
-    if (threadIdx.x == 0) counts[scene] = c;
-    // counting rank: the number of keys above mine
-    for (int j0 = 0; j0 < c; j0 += kDetThreads) {
-        const int j = j0 + threadIdx.x;
-        const unsigned long long mine = keys[min(j, c - 1)];
-        int rank = 0;
-        for (int k = 0; k < c; ++k) rank += keys[k] > mine ? 1 : 0;
-        if (j < c) {
-            const int src = (int)(~(unsigned)mine);
-            const float *p = boxes3d + (size_t)src * 7;
-            const float half_l = p[5] / 2, half_w = p[4] / 2;
-            sel[rank] = src;
-            bev[rank * 5 + 0] = p[0] - half_l;
-            bev[rank * 5 + 1] = p[2] - half_w;
-            bev[rank * 5 + 2] = p[0] + half_l;
-            bev[rank * 5 + 3] = p[2] + half_w;
-            bev[rank * 5 + 4] = p[6];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void det_emit_kernel(int m, const float *__restrict__ boxes3d,
-                                                       const float *__restrict__ raw_scores, const int *__restrict__ sel,
-                                                       const long long *__restrict__ keep, const int *__restrict__ num_keep,
-                                                       float *__restrict__ det_boxes3d, float *__restrict__ det_scores,
-                                                       int *__restrict__ det_count) {
-    const int scene = blockIdx.x;
-    const int kept = min(num_keep[scene], m);
-    if (threadIdx.x == 0) det_count[scene] = kept;
-    for (int j = threadIdx.x; j < m; j += 256) {
-        float row[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float sc = 0.f;
-        if (j < kept) {
-            const int src = sel[(size_t)scene * m + (int)keep[(size_t)scene * m + j]];
-#pragma unroll
-            for (int q = 0; q < 7; ++q) row[q] = boxes3d[((size_t)scene * m + src) * 7 + q];
-            sc = raw_scores[(size_t)scene * m + src];
-        }
-#pragma unroll
-        for (int q = 0; q < 7; ++q) det_boxes3d[((size_t)scene * m + j) * 7 + q] = row[q];
-        det_scores[(size_t)scene * m + j] = sc;
-    }
-}
-
-// ---- RCNN training targets: ROI sampling (lib/rpn/proposal_target_layer.py:85-218, sample_rois_for_rcnn) ---------------------
-// The reference walks the scenes on the host: three `nonzero` syncs per scene, np.random.permutation / torch.randint on the
-// host, index uploads. Here: (0) one workgroup per scene counts the box rows; (1) the (ROI, ground truth) pairs of a scene are spread over the lanes of ceil(m / (256 / g))
-// workgroups, every IoU is iou3d_pair -- bit for bit epnet_boxes_iou3d's -- and lands in the workspace matrix; (2) ONE
-// workgroup per scene folds each row to its maximum and first arg-max, compacts the three class lists in ascending ROI
-// index (ballot + prefix, as proposal_bin_kernel), ranks the foreground candidates by the caller's keys, fills the R slots
-// from the caller's uniform draws and gathers the rows. No value leaves the device, nothing depends on a launch order.
-constexpr int kSmpThreads = 1024;
-constexpr int kSmpMaxM = 4096;
-constexpr int kSmpMaxR = 1024;
-// ROIs per workgroup of the IoU phase: as many as give every thread ONE pair when all g rows count (a pair is a long chain of
-// dependent arithmetic -- about 20 us -- so the phase lasts as long as the longest thread's list of pairs)
-static inline int smp_rois_per_block(int g) { return g >= 256 ? 1 : 256 / g; }
-
-// 1 + the last row whose fp32 sum over all gc columns (ascending) is not 0; 0 without such a row. Every thread of the
-// workgroup gets the result; s_red holds one int per wave.
-__device__ __forceinline__ int count_gt_rows(int g, int gc, const float *__restrict__ gt, int *s_red) {
-    int last = 0;
-    for (int r = threadIdx.x; r < g; r += blockDim.x) {
-        float sum = 0.f;
-        for (int c = 0; c < gc; ++c) sum = sum + gt[(size_t)r * gc + c];
-        if (sum != 0.f) last = r + 1;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
-    if (lane_id() == 0) s_red[threadIdx.x >> 6] = last;
-    __syncthreads();
-    int res = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) res = max(res, s_red[w]);
-    __syncthreads();
-    return res;
-}
-
-// one workgroup per scene reads the box table ONCE (the IoU phase has up to m workgroups per scene)
-__global__ __launch_bounds__(256) void rcnn_count_gt_kernel(int g, int gc, const float *__restrict__ gt, int *__restrict__ num_gt_out) {
-    __shared__ int s_red[4];
-    const int scene = blockIdx.x;
-    const int counted = count_gt_rows(g, gc, gt + (size_t)scene * g * gc, s_red);
-    if (threadIdx.x == 0) num_gt_out[scene] = counted;
-}
-
-__global__ __launch_bounds__(256) void rcnn_iou_kernel(int m, int g, int gc, int rois_per_block, const float *__restrict__ rois,
-                                                       const float *__restrict__ gt, float *__restrict__ iou_mat,
-                                                       const int *__restrict__ num_gt_in) {
-    const int scene = blockIdx.y, first = blockIdx.x * rois_per_block;
-    rois += (size_t)scene * m * 7;
-    gt += (size_t)scene * g * gc;
-    iou_mat += (size_t)scene * m * g;
-    const int num_gt = max(num_gt_in[scene], 1);  // a scene without ground truth: the zero row 0 alone, every IoU 0
-    const int n_roi = min(rois_per_block, m - first);
-    const long long pairs = (long long)n_roi * num_gt;
-    for (long long p = threadIdx.x; p < pairs; p += 256) {
-        const int i = first + (int)(p / num_gt), j = (int)(p % num_gt);
-        float a7[7], b7[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) {
-            a7[q] = rois[(size_t)i * 7 + q];
-            b7[q] = gt[(size_t)j * gc + q];
-        }
-        iou_mat[(size_t)i * g + j] = iou3d_pair(a7, b7);
-    }
-}
-
-// pick(list, u) of include/epnet_ops.h: entry min((int)(u * (float)len), len - 1), entry 0 for a NaN or negative u
-__device__ __forceinline__ int pick_pos(float u, int len) {
-    const float p = u * (float)len;
-    if (!(p >= 0.f)) return 0;
-    return p >= (float)len ? len - 1 : (int)p;
-}
-
-// the maximum of a row and the FIRST column that reaches it; a NaN wins over every number and then stays
-__device__ __forceinline__ float row_max_first(const float *__restrict__ row, int n, int &arg) {
-    float best = row[0];
-    arg = 0;
-    for (int j = 1; j < n; ++j) {
-        const float v = row[j];
-        if (v > best || (v != v && best == best)) {
-            best = v;
-            arg = j;
-        }
-    }
-    return best;
-}
-
-__global__ __launch_bounds__(kSmpThreads) void rcnn_select_kernel(
-    int m, int g, int gc, int per_image, int fg_per_image, float fg_thresh, float bg_thresh, float bg_thresh_lo,
-    double hard_bg_ratio, int aug_times, const float *__restrict__ rois, const float *__restrict__ gt,
-    const float *__restrict__ fg_key, const float *__restrict__ slot_u, const float *__restrict__ iou_mat,
-    const int *__restrict__ num_gt_in, float *__restrict__ max_overlaps, int *__restrict__ gt_assignment,
-    float *__restrict__ batch_rois, float *__restrict__ batch_gt, float *__restrict__ iou_src, int *__restrict__ tries,
-    float *__restrict__ roi_iou_direct, int *__restrict__ src_inds, int *__restrict__ scene_info) {
-    __shared__ unsigned short lists[3][kSmpMaxM];  // fg, hard, easy: ROI indices in ascending order
-    __shared__ unsigned long long keys[kSmpMaxM];
-    __shared__ int slot_src[kSmpMaxR];
-    __shared__ int wave_cnt[3][kSmpThreads / 64];
-    __shared__ int base[3];
-    const int scene = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6;
-    rois += (size_t)scene * m * 7;
-    gt += (size_t)scene * g * gc;
-    fg_key += (size_t)scene * m;
-    slot_u += (size_t)scene * per_image;
-    iou_mat += (size_t)scene * m * g;
-    max_overlaps += (size_t)scene * m;
-    gt_assignment += (size_t)scene * m;
-    const int counted = num_gt_in[scene];
-    const int num_gt = max(counted, 1);
-    if (threadIdx.x < 3) base[threadIdx.x] = 0;
-    __syncthreads();
-    for (int start = 0; start < m; start += kSmpThreads) {
-        const int i = start + threadIdx.x;
-        bool in[3] = {false, false, false};
-        if (i < m) {
-            int arg;
-            const float best = row_max_first(iou_mat + (size_t)i * g, num_gt, arg);
-            max_overlaps[i] = best;
-            gt_assignment[i] = arg;
-            in[0] = best >= fg_thresh;                                   // :117
-            in[1] = best < bg_thresh && best >= bg_thresh_lo;             // :123-124
-            in[2] = best < bg_thresh_lo;                                  // :122
-        }
-        unsigned long long mk[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            mk[c] = __ballot(in[c]);
-            if (lane == 0) wave_cnt[c][wave] = (int)__popcll(mk[c]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if (in[c]) {
-                int before = base[c];
-                for (int w = 0; w < wave; ++w) before += wave_cnt[c][w];
-                lists[c][before + popc_below(mk[c])] = (unsigned short)i;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            int t = 0;
-            for (int w = 0; w < kSmpThreads / 64; ++w) t += wave_cnt[threadIdx.x][w];
-            base[threadIdx.x] += t;
-        }
-        __syncthreads();
-    }
-    const int fg_num = base[0], hard_num = base[1], easy_num = base[2], bg_num = hard_num + easy_num;
-    const int which = fg_num > 0 ? (bg_num > 0 ? 0 : 1) : (bg_num > 0 ? 2 : 3);
-    const int fg_this = which == 0 ? min(fg_per_image, fg_num) : which == 1 ? per_image : 0;
-    if (which == 0) {
-        // the fg_this smallest keys in ascending (key, ROI index) order: a counting rank over unique 64-bit keys
-        for (int q = threadIdx.x; q < fg_num; q += kSmpThreads) {
-            const unsigned roi = lists[0][q];
-            keys[q] = ((unsigned long long)ordered_key(fg_key[roi]) << 32) | roi;
-        }
-        __syncthreads();
-        for (int q = threadIdx.x; q < fg_num; q += kSmpThreads) {
-            const unsigned long long mine = keys[q];
-            int rank = 0;
-            for (int k = 0; k < fg_num; ++k) rank += keys[k] < mine ? 1 : 0;
-            if (rank < fg_this) slot_src[rank] = (int)(unsigned)mine;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int *info = scene_info + (size_t)scene * 6;
-        info[0] = counted;
-        info[1] = fg_num;
-        info[2] = hard_num;
-        info[3] = easy_num;
-        info[4] = fg_this;
-        info[5] = which;
-    }
-    const int bg_tries = aug_times > 0 ? 1 : 0;  // :174
-    for (int j = threadIdx.x; j < per_image; j += kSmpThreads) {
-        const float u = slot_u[j];
-        int src;
-        if (which == 3) {
-            src = pick_pos(u, m);
-        } else if (which == 1) {
-            src = lists[0][pick_pos(u, fg_num)];
-        } else if (j < fg_this) {
-            src = slot_src[j];
-        } else if (hard_num > 0 && easy_num > 0) {  // :194-206
-            const int hard_slots = (int)((double)(per_image - fg_this) * hard_bg_ratio);
-            src = j - fg_this < hard_slots ? lists[1][pick_pos(u, hard_num)] : lists[2][pick_pos(u, easy_num)];
-        } else if (hard_num > 0) {
-            src = lists[1][pick_pos(u, hard_num)];
-        } else {
-            src = lists[2][pick_pos(u, easy_num)];
-        }
-        const size_t o = (size_t)scene * per_image + j;
-        int assigned;  // folded again from the matrix of the IoU launch rather than read back from this launch's own stores
-        const float ov = row_max_first(iou_mat + (size_t)src * g, num_gt, assigned);
-#pragma unroll
-        for (int q = 0; q < 7; ++q) {
-            batch_rois[o * 7 + q] = rois[(size_t)src * 7 + q];
-            batch_gt[o * 7 + q] = gt[(size_t)assigned * gc + q];
-        }
-        iou_src[o] = ov;
-        tries[o] = j < fg_this ? aug_times : bg_tries;
-        if (roi_iou_direct) roi_iou_direct[o] = ov;
-        if (src_inds) src_inds[o] = src;
-    }
-}
-
-// ---- evaluation recall (tools/eval_rcnn.py:598-632) ---------------------------------------------------------------------------
-// The reference walks the scenes on the host: it trims the padded ground truth, calls boxes_iou3d_gpu for the refined boxes and
-// for the ROIs, and reads `(gt_max_iou > thresh).sum().item()` ten times and the segmentation IoU once -- about a dozen syncs
-// per scene. Here: (1) one workgroup per (scene, box set, ground-truth row) puts its lanes over the boxes, every IoU is
-// iou3d_pair -- bit for bit epnet_boxes_iou3d's -- and the column maximum is folded across the wave on the vector ALU (dpp.h)
-// and across the waves through LDS; (2) the segmentation counts are a grid-stride integer reduction into one partial per
-// workgroup; (3) one workgroup per scene counts the thresholds, folds the rows for pred_max_iou and adds the epoch totals
-// (integer atomics: the order does not matter), and workgroup 0 adds the segmentation partials. The cost is the latency of one
-// rotated-box IoU per lane, not bytes. No value leaves the device.
-constexpr int kEvalMaxM = 4096;
-constexpr int kEvalMaxT = 8;
-constexpr int kEvalSegBlocks = 256;  // most workgroups of the segmentation reduction (the partials' room in the workspace)
-
-struct EvalThresholds {
-    float v[kEvalMaxT];
-};
-
-// float <-> int, order preserving (its own inverse), every NaN on top: the maximum over these keys is the maximum that
-// propagates a NaN, as torch.max does. -0.0 ranks below +0.0.
-__device__ __forceinline__ int max_key(float v) {
-    if (v != v) return 0x7fffffff;
-    const int s = __float_as_int(v);
-    return s >= 0 ? s : s ^ 0x7fffffff;
-}
-__device__ __forceinline__ float max_key_value(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
-
-__global__ __launch_bounds__(256) void eval_iou_kernel(int m, int g, int gc, const float *__restrict__ pred,
-                                                       const float *__restrict__ roi, const float *__restrict__ gt,
-                                                       float *__restrict__ gt_max, float *__restrict__ mat) {
-    __shared__ int s_red[4];
-    __shared__ int s_key[4];
-    const int j = blockIdx.x, set = blockIdx.y, scene = blockIdx.z;
-    gt += (size_t)scene * g * gc;
-    const float *boxes = (set == 0 ? pred : roi) + (size_t)scene * m * 7;
-    const int num_gt = count_gt_rows(g, gc, gt, s_red);
-    int key = (int)0x80000000;  // below every key
-    if (j < num_gt) {  // uniform over the workgroup
-        float b7[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) b7[q] = gt[(size_t)j * gc + q];
-        for (int i = threadIdx.x; i < m; i += 256) {
-            float a7[7];
-#pragma unroll
-            for (int q = 0; q < 7; ++q) a7[q] = boxes[(size_t)i * 7 + q];
-            const float v = iou3d_pair(a7, b7);
-            key = max(key, max_key(v));
-            if (mat && set == 0) mat[((size_t)scene * g + j) * m + i] = v;
-        }
-    }
-    key = wave_max_all(key);  // all 64 lanes active
-    if (lane_id() == 0) s_key[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int k = max(max(s_key[0], s_key[1]), max(s_key[2], s_key[3]));
-        gt_max[((size_t)scene * 2 + set) * g + j] = j < num_gt ? max_key_value(k) : 0.f;
-    }
-}
-
-// one partial [correct, fg, pos] per workgroup (a few hundred KB of int32 per batch: plain coalesced loads)
-__global__ __launch_bounds__(256) void eval_seg_kernel(long long total, const int *__restrict__ seg, const int *__restrict__ label,
-                                                       long long *__restrict__ partial) {
-    __shared__ long long s_sum[4][3];
-    long long c = 0, f = 0, p = 0;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
-        const int s = seg[e], l = label[e];
-        c += (l > 0 && s == l) ? 1 : 0;
-        f += l > 0 ? 1 : 0;
-        p += s > 0 ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        c += __shfl_xor(c, off, 64);
-        f += __shfl_xor(f, off, 64);
-        p += __shfl_xor(p, off, 64);
-    }
-    if (lane_id() == 0) {
-        s_sum[threadIdx.x >> 6][0] = c;
-        s_sum[threadIdx.x >> 6][1] = f;
-        s_sum[threadIdx.x >> 6][2] = p;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        partial[(size_t)blockIdx.x * 3 + threadIdx.x] = s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x] + s_sum[2][threadIdx.x] + s_sum[3][threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void eval_finish_kernel(int m, int g, int gc, int nt, EvalThresholds thr, int have_roi,
-                                                          const float *__restrict__ gt, const float *__restrict__ gt_max,
-                                                          const float *__restrict__ mat, const long long *__restrict__ seg_partial,
-                                                          int seg_blocks, int *__restrict__ scene_stats,
-                                                          long long *__restrict__ seg_counts, unsigned long long *__restrict__ totals,
-                                                          float *__restrict__ gt_max_pred, float *__restrict__ gt_max_roi,
-                                                          float *__restrict__ pred_max_iou) {
-    __shared__ int s_red[4];
-    __shared__ int s_cnt[2][kEvalMaxT];
-    const int scene = blockIdx.x;
-    const int num_gt = count_gt_rows(g, gc, gt + (size_t)scene * g * gc, s_red);
-    if (threadIdx.x < 2 * kEvalMaxT) s_cnt[threadIdx.x / kEvalMaxT][threadIdx.x % kEvalMaxT] = 0;
-    __syncthreads();
-    for (int j = threadIdx.x; j < g; j += 256) {
-        const float vp = j < num_gt ? gt_max[((size_t)scene * 2 + 0) * g + j] : 0.f;
-        const float vr = (have_roi && j < num_gt) ? gt_max[((size_t)scene * 2 + 1) * g + j] : 0.f;
-        if (gt_max_pred) gt_max_pred[(size_t)scene * g + j] = vp;
-        if (gt_max_roi) gt_max_roi[(size_t)scene * g + j] = vr;
-        if (j < num_gt) {
-            for (int t = 0; t < nt; ++t) {  // strict, fp32; a NaN maximum is above no threshold (:615, :625)
-                if (vp > thr.v[t]) atomicAdd(&s_cnt[0][t], 1);
-                if (have_roi && vr > thr.v[t]) atomicAdd(&s_cnt[1][t], 1);
-            }
-        }
-    }
-    __syncthreads();
-    const int cols = 1 + 2 * nt;
-    if ((int)threadIdx.x < cols) {
-        const int t = threadIdx.x;
-        const int v = t == 0 ? num_gt : (t <= nt ? s_cnt[0][t - 1] : s_cnt[1][t - 1 - nt]);
-        scene_stats[(size_t)scene * cols + t] = v;
-        if (totals && v != 0) atomicAdd(&totals[t], (unsigned long long)v);
-    }
-    if (pred_max_iou) {
-        for (int i = threadIdx.x; i < m; i += 256) {
-            int key = (int)0x80000000;
-            for (int j = 0; j < num_gt; ++j) key = max(key, max_key(mat[((size_t)scene * g + j) * m + i]));
-            pred_max_iou[(size_t)scene * m + i] = num_gt > 0 ? max_key_value(key) : 0.f;
-        }
-    }
-    if (scene == 0 && seg_counts && threadIdx.x < 3) {
-        long long sum = 0;
-        for (int w = 0; w < seg_blocks; ++w) sum += seg_partial[(size_t)w * 3 + threadIdx.x];
-        seg_counts[threadIdx.x] = sum;
-    }
 }
 
 }  // namespace epnet
@@ -1270,18 +393,33 @@ extern "C" int epnet_boxes_iou_bev(int num_a, const float *boxes_a, int num_b, c
 
 extern "C" size_t epnet_nms_workspace_bytes(int boxes_num) {
     if (boxes_num <= 0) return 0;
-    const size_t col_blocks = ((size_t)boxes_num + 63) / 64;
-    return (size_t)boxes_num * col_blocks * sizeof(unsigned long long) + (size_t)boxes_num * sizeof(BoxRot);
+    return (size_t)boxes_num * nms_mask_words((size_t)boxes_num) * sizeof(unsigned long long) + (size_t)boxes_num * sizeof(BoxRot);
+}
+
+// argument checks and the zero-box case of epnet_nms / epnet_nms_normal; the rest is ONE group of boxes_num boxes
+static int nms_single(bool rotated, const float *boxes, int boxes_num, float thresh, void *workspace, size_t workspace_bytes,
+                      int64_t *keep, int *num_keep, hipStream_t s) {
+    if (boxes_num < 0) return EPNET_EINVAL;
+    if (!num_keep) return EPNET_EINVAL;
+    if (boxes_num == 0) {
+        hipError_t e = hipMemsetAsync(num_keep, 0, sizeof(int), s);
+        return e == hipSuccess ? EPNET_OK : record_hip_error(e, "nms memset");
+    }
+    if (!(boxes && keep && workspace)) return EPNET_EINVAL;
+    if (workspace_bytes < epnet_nms_workspace_bytes(boxes_num)) return EPNET_ENOMEM;
+    unsigned long long *mask = (unsigned long long *)workspace;
+    BoxRot *rot = (BoxRot *)(mask + (size_t)boxes_num * nms_mask_words((size_t)boxes_num));
+    return nms_groups(rotated, 1, boxes_num, /*counts*/ nullptr, boxes, thresh, rot, mask, (long long *)keep, num_keep, s);
 }
 
 extern "C" int epnet_nms(const float *boxes, int boxes_num, float thresh, void *workspace, size_t workspace_bytes,
                          int64_t *keep, int *num_keep, epnet_stream_t stream) {
-    return nms_impl<true>(boxes, boxes_num, thresh, workspace, workspace_bytes, keep, num_keep, (hipStream_t)stream);
+    return nms_single(true, boxes, boxes_num, thresh, workspace, workspace_bytes, keep, num_keep, (hipStream_t)stream);
 }
 
 extern "C" int epnet_nms_normal(const float *boxes, int boxes_num, float thresh, void *workspace,
                                 size_t workspace_bytes, int64_t *keep, int *num_keep, epnet_stream_t stream) {
-    return nms_impl<false>(boxes, boxes_num, thresh, workspace, workspace_bytes, keep, num_keep, (hipStream_t)stream);
+    return nms_single(false, boxes, boxes_num, thresh, workspace, workspace_bytes, keep, num_keep, (hipStream_t)stream);
 }
 
 extern "C" int epnet_boxes_iou3d(int num_a, const float *boxes_a, int num_b, const float *boxes_b, float *ans,
@@ -1302,288 +440,4 @@ extern "C" int epnet_boxes_iou3d_pairs(int k, const float *boxes_a, const float 
     EPNET_REQUIRE(boxes_a && boxes_b && ans);
     hipLaunchKernelGGL(iou3d_pairs_kernel, dim3(div_up(k, 256)), dim3(256), 0, (hipStream_t)stream, k, boxes_a, boxes_b, ans);
     return check_launch("boxes_iou3d_pairs");
-}
-
-// the noise loop over k ROIs: the wave form up to 64 tries, the serial form beyond (arguments already checked)
-static int aug_roi_launch(int k, int aug_times, float pos_thresh, float *roi_boxes3d, const float *gt_boxes3d,
-                          const float *iou3d_src, const int *tries, const unsigned char *keep_draw, const float *noise,
-                          float *iou_of_rois, hipStream_t s) {
-    if (aug_times >= 1 && aug_times <= 64 && 0.f < pos_thresh) {  // (the loop starts from temp_iou = 0, :225)
-        int tp = 1;
-        while (tp < aug_times) tp *= 2;
-        const int per_wave = 64 / tp;
-        const int waves = div_up(k, per_wave);
-        hipLaunchKernelGGL(aug_roi_wave_kernel, dim3(div_up(waves, 4)), dim3(256), 0, s, k, aug_times, tp, pos_thresh,
-                           roi_boxes3d, gt_boxes3d, iou3d_src, tries, keep_draw, noise, iou_of_rois);
-    } else {
-        hipLaunchKernelGGL(aug_roi_serial_kernel, dim3(div_up(k, 64)), dim3(64), 0, s, k, aug_times, pos_thresh, roi_boxes3d,
-                           gt_boxes3d, iou3d_src, tries, keep_draw, noise, iou_of_rois);
-    }
-    return check_launch("aug_roi_by_noise");
-}
-
-extern "C" int epnet_aug_roi_by_noise(int k, int aug_times, float pos_thresh, float *roi_boxes3d, const float *gt_boxes3d,
-                                      const float *iou3d_src, const int *tries, const unsigned char *keep_draw,
-                                      const float *noise, float *iou_of_rois, epnet_stream_t stream) {
-    EPNET_REQUIRE(k >= 0 && aug_times >= 0);
-    if (k == 0) return EPNET_OK;
-    EPNET_REQUIRE(roi_boxes3d && gt_boxes3d && iou3d_src && iou_of_rois);
-    EPNET_REQUIRE(aug_times == 0 || (keep_draw && noise));
-    return aug_roi_launch(k, aug_times, pos_thresh, roi_boxes3d, gt_boxes3d, iou3d_src, tries, keep_draw, noise, iou_of_rois,
-                          (hipStream_t)stream);
-}
-
-namespace {
-struct SamplePlan {
-    size_t off_num_gt, off_mat, off_max, off_assign, off_tries, off_iou_src, bytes;
-};
-
-inline size_t smp_align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-SamplePlan sample_plan(int b, int m, int g, int r) {
-    SamplePlan p;
-    const size_t sb = (size_t)b, sm = (size_t)m, sg = (size_t)g, sr = (size_t)r;
-    size_t off = 0;
-    p.off_num_gt = off;  off = smp_align16(off + sb * sizeof(int));
-    p.off_mat = off;     off = smp_align16(off + sb * sm * sg * sizeof(float));
-    p.off_max = off;     off = smp_align16(off + sb * sm * sizeof(float));
-    p.off_assign = off;  off = smp_align16(off + sb * sm * sizeof(int));
-    p.off_tries = off;   off = smp_align16(off + sb * sr * sizeof(int));
-    p.off_iou_src = off; off = smp_align16(off + sb * sr * sizeof(float));
-    p.bytes = off;
-    return p;
-}
-}  // namespace
-
-extern "C" size_t epnet_rcnn_sample_rois_workspace_bytes(int b, int m, int g, int r) {
-    if (b <= 0 || b > 65535 || m < 1 || m > kSmpMaxM || g < 1 || r < 1 || r > kSmpMaxR) return 0;
-    return sample_plan(b, m, g, r).bytes;
-}
-
-extern "C" int epnet_rcnn_sample_rois(int b, int m, int g, int gc, int r, int fg_per_image, float fg_thresh, float cls_bg_thresh,
-                                      float cls_bg_thresh_lo, double hard_bg_ratio, int aug_times, const float *rois,
-                                      const float *gt_boxes3d, const float *fg_key, const float *slot_u,
-                                      const unsigned char *keep_draw, const float *noise, void *workspace,
-                                      size_t workspace_bytes, float *batch_rois, float *batch_gt_of_rois, float *batch_roi_iou,
-                                      int *scene_info, int *src_inds, float *iou_src, int *tries, float *max_overlaps,
-                                      int *gt_assignment, epnet_stream_t stream) {
-    EPNET_REQUIRE(b >= 0 && m >= 0 && g >= 0 && r >= 0 && aug_times >= 0 && fg_per_image >= 0);
-    if (b == 0) return EPNET_OK;
-    if (m < 1 || m > kSmpMaxM || r < 1 || r > kSmpMaxR || g < 1 || b > 65535) return EPNET_ELIMIT;
-    EPNET_REQUIRE(gc >= 7 && gc <= 16 && fg_per_image <= r);
-    EPNET_REQUIRE(rois && gt_boxes3d && fg_key && slot_u && workspace && batch_rois && batch_gt_of_rois && batch_roi_iou && scene_info);
-    EPNET_REQUIRE(aug_times == 0 || (keep_draw && noise));
-    const SamplePlan p = sample_plan(b, m, g, r);
-    if (workspace_bytes < p.bytes) return EPNET_ENOMEM;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int *num_gt = (int *)(ws + p.off_num_gt);
-    float *mat = (float *)(ws + p.off_mat);
-    float *mo = max_overlaps ? max_overlaps : (float *)(ws + p.off_max);
-    int *as = gt_assignment ? gt_assignment : (int *)(ws + p.off_assign);
-    int *tr = tries ? tries : (int *)(ws + p.off_tries);
-    float *src_iou = iou_src ? iou_src : (float *)(ws + p.off_iou_src);
-    const int per_block = smp_rois_per_block(g);
-    hipLaunchKernelGGL(rcnn_count_gt_kernel, dim3(b), dim3(256), 0, s, g, gc, gt_boxes3d, num_gt);
-    int rc = check_launch("rcnn_sample_rois count");
-    if (rc) return rc;
-    hipLaunchKernelGGL(rcnn_iou_kernel, dim3(div_up(m, per_block), b), dim3(256), 0, s, m, g, gc, per_block, rois, gt_boxes3d, mat,
-                       (const int *)num_gt);
-    rc = check_launch("rcnn_sample_rois iou");
-    if (rc) return rc;
-    hipLaunchKernelGGL(rcnn_select_kernel, dim3(b), dim3(kSmpThreads), 0, s, m, g, gc, r, fg_per_image, fg_thresh, cls_bg_thresh,
-                       cls_bg_thresh_lo, hard_bg_ratio, aug_times, rois, gt_boxes3d, fg_key, slot_u, (const float *)mat,
-                       (const int *)num_gt, mo, as, batch_rois, batch_gt_of_rois, src_iou, tr,
-                       aug_times == 0 ? batch_roi_iou : (float *)nullptr, src_inds, scene_info);
-    rc = check_launch("rcnn_sample_rois select");
-    if (rc || aug_times == 0) return rc;
-    // the noise loop (:158-179) over all b * r rows: foreground slots get aug_times tries, background slots one
-    return aug_roi_launch(b * r, aug_times, fg_thresh, batch_rois, batch_gt_of_rois, src_iou, tr, keep_draw, noise, batch_roi_iou, s);
-}
-
-namespace {
-struct ProposalPlan {
-    int bins, pre0, pre1, post0, post1, cap, groups;
-    size_t off_counts, off_num_keep, off_sel, off_bev, off_trig, off_keep, off_mask, bytes;
-};
-
-inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// pre / post budgets of the two distance bins: int(0.7 * total) and the rest (proposal_layer.py:66-69)
-ProposalPlan proposal_plan(int b, int distance_based, int pre_nms_top_n, int post_nms_top_n) {
-    ProposalPlan p;
-    p.bins = distance_based ? 2 : 1;
-    p.pre0 = distance_based ? (int)(pre_nms_top_n * 0.7) : pre_nms_top_n;
-    p.pre1 = pre_nms_top_n - p.pre0;
-    p.post0 = distance_based ? (int)(post_nms_top_n * 0.7) : post_nms_top_n;
-    p.post1 = post_nms_top_n - p.post0;
-    p.cap = p.pre0 > p.pre1 ? p.pre0 : p.pre1;
-    if (p.cap < 1) p.cap = 1;
-    p.groups = b * 2;
-    const size_t g = (size_t)p.groups, cap = (size_t)p.cap, tot = (size_t)(p.pre0 + p.pre1);
-    size_t off = 0;
-    p.off_counts = off;   off = align16(off + g * sizeof(int));
-    p.off_num_keep = off; off = align16(off + g * sizeof(int));
-    p.off_sel = off;      off = align16(off + g * tot * sizeof(int));
-    p.off_bev = off;      off = align16(off + g * cap * 5 * sizeof(float));
-    p.off_trig = off;     off = align16(off + g * cap * sizeof(epnet::BoxRot));
-    p.off_keep = off;     off = align16(off + g * cap * sizeof(long long));
-    p.off_mask = off;     off = align16(off + g * cap * ((cap + 63) / 64) * sizeof(unsigned long long));
-    p.bytes = off;
-    return p;
-}
-}  // namespace
-
-extern "C" size_t epnet_rpn_proposals_workspace_bytes(int b, int distance_based, int pre_nms_top_n, int post_nms_top_n) {
-    if (b <= 0 || pre_nms_top_n < 0 || post_nms_top_n < 0) return 0;
-    return proposal_plan(b, distance_based, pre_nms_top_n, post_nms_top_n).bytes;
-}
-
-extern "C" int epnet_rpn_proposals(int b, int n, const float *proposals, const float *scores, const int64_t *order,
-                                   int distance_based, int pre_nms_top_n, int post_nms_top_n, float nms_thresh, int rotated,
-                                   void *workspace, size_t workspace_bytes, float *ret_bbox3d, float *ret_scores, int *ret_count,
-                                   epnet_stream_t stream) {
-    EPNET_REQUIRE(b >= 0 && n >= 0 && pre_nms_top_n >= 0 && post_nms_top_n >= 0);
-    if (b == 0 || post_nms_top_n == 0) return EPNET_OK;
-    EPNET_REQUIRE(ret_bbox3d && ret_scores && workspace);
-    EPNET_REQUIRE(n == 0 || (proposals && scores && order));
-    const ProposalPlan p = proposal_plan(b, distance_based, pre_nms_top_n, post_nms_top_n);
-    if (workspace_bytes < p.bytes) return EPNET_ENOMEM;
-    if (b > 32767) return EPNET_ELIMIT;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int *counts = (int *)(ws + p.off_counts), *num_keep = (int *)(ws + p.off_num_keep), *sel = (int *)(ws + p.off_sel);
-    float *bev = (float *)(ws + p.off_bev);
-    BoxRot *trig = (BoxRot *)(ws + p.off_trig);
-    long long *keep = (long long *)(ws + p.off_keep);
-    unsigned long long *mask = (unsigned long long *)(ws + p.off_mask);
-    hipLaunchKernelGGL(proposal_bin_kernel, dim3(b), dim3(kBinThreads), 0, s, n, p.bins, p.pre0, p.pre1, p.cap, proposals,
-                       (const long long *)order, sel, counts, bev);
-    int rc = check_launch("rpn_proposals bin");
-    if (rc) return rc;
-    rc = nms_groups(rotated != 0, p.groups, p.cap, counts, bev, nms_thresh, trig, mask, keep, num_keep, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(proposal_emit_kernel, dim3(b), dim3(256), 0, s, n, p.pre0, p.pre1, p.cap, p.post0, p.post1, proposals, scores,
-                       (const long long *)order, sel, keep, num_keep, ret_bbox3d, ret_scores, ret_count);
-    return check_launch("rpn_proposals emit");
-}
-
-
-namespace {
-struct DetPlan {
-    size_t off_counts, off_num_keep, off_sel, off_bev, off_rot, off_keep, off_mask, bytes;
-};
-
-DetPlan det_plan(int b, int m) {
-    DetPlan p;
-    const size_t g = (size_t)b, cap = (size_t)m;
-    size_t off = 0;
-    p.off_counts = off;   off = align16(off + g * sizeof(int));
-    p.off_num_keep = off; off = align16(off + g * sizeof(int));
-    p.off_sel = off;      off = align16(off + g * cap * sizeof(int));
-    p.off_bev = off;      off = align16(off + g * cap * 5 * sizeof(float));
-    p.off_rot = off;      off = align16(off + g * cap * sizeof(epnet::BoxRot));
-    p.off_keep = off;     off = align16(off + g * cap * sizeof(long long));
-    p.off_mask = off;     off = align16(off + g * cap * ((cap + 63) / 64) * sizeof(unsigned long long));
-    p.bytes = off;
-    return p;
-}
-}  // namespace
-
-extern "C" size_t epnet_rcnn_detections_workspace_bytes(int b, int m) {
-    if (b <= 0 || m < 1 || m > kDetMaxM || b > 65535) return 0;
-    return det_plan(b, m).bytes;
-}
-
-extern "C" int epnet_rcnn_detections(int b, int m, const float *boxes3d, const float *raw_scores, const float *norm_scores,
-                                     float score_thresh, float nms_thresh, void *workspace, size_t workspace_bytes,
-                                     float *det_boxes3d, float *det_scores, int *det_count, epnet_stream_t stream) {
-    EPNET_REQUIRE(b >= 0 && m >= 0);
-    if (b == 0) return EPNET_OK;
-    if (m < 1 || m > kDetMaxM || b > 65535) return EPNET_ELIMIT;
-    EPNET_REQUIRE(boxes3d && raw_scores && norm_scores && workspace && det_boxes3d && det_scores && det_count);
-    const DetPlan p = det_plan(b, m);
-    if (workspace_bytes < p.bytes) return EPNET_ENOMEM;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int *counts = (int *)(ws + p.off_counts), *num_keep = (int *)(ws + p.off_num_keep), *sel = (int *)(ws + p.off_sel);
-    float *bev = (float *)(ws + p.off_bev);
-    BoxRot *rot = (BoxRot *)(ws + p.off_rot);
-    long long *keep = (long long *)(ws + p.off_keep);
-    unsigned long long *mask = (unsigned long long *)(ws + p.off_mask);
-    hipLaunchKernelGGL(det_select_kernel, dim3(b), dim3(kDetThreads), 0, s, m, score_thresh, boxes3d, raw_scores, norm_scores, sel,
-                       counts, bev);
-    int rc = check_launch("rcnn_detections select");
-    if (rc) return rc;
-    rc = nms_groups(true, b, m, counts, bev, nms_thresh, rot, mask, keep, num_keep, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(det_emit_kernel, dim3(b), dim3(256), 0, s, m, boxes3d, raw_scores, sel, keep, num_keep, det_boxes3d,
-                       det_scores, det_count);
-    return check_launch("rcnn_detections emit");
-}
-
-namespace {
-struct EvalPlan {
-    size_t off_seg, off_gt_max, off_mat, bytes;
-};
-
-EvalPlan eval_plan(int b, int m, int g) {
-    EvalPlan p;
-    const size_t sb = (size_t)b, sm = (size_t)m, sg = (size_t)g;
-    size_t off = 0;
-    p.off_seg = off;    off = align16(off + (size_t)kEvalSegBlocks * 3 * sizeof(long long));
-    p.off_gt_max = off; off = align16(off + sb * 2 * sg * sizeof(float));
-    p.off_mat = off;    off = align16(off + sb * sg * sm * sizeof(float));
-    p.bytes = off;
-    return p;
-}
-}  // namespace
-
-extern "C" size_t epnet_eval_recall_workspace_bytes(int b, int m, int g) {
-    if (b <= 0 || b > 65535 || m < 1 || m > kEvalMaxM || g < 0) return 0;
-    return eval_plan(b, m, g).bytes;
-}
-
-extern "C" int epnet_eval_recall(int b, int m, int g, int gc, int n, int nt, const float *thresholds, const float *pred_boxes3d,
-                                 const float *roi_boxes3d, const float *gt_boxes3d, const int *seg_result, const int *rpn_cls_label,
-                                 void *workspace, size_t workspace_bytes, int *scene_stats, int64_t *seg_counts, int64_t *totals,
-                                 float *gt_max_pred, float *gt_max_roi, float *pred_max_iou, epnet_stream_t stream) {
-    EPNET_REQUIRE(b >= 0 && m >= 0 && n >= 0 && nt >= 0);
-    if (b == 0) return EPNET_OK;
-    if (m < 1 || m > kEvalMaxM || g < 0 || b > 65535 || nt > kEvalMaxT) return EPNET_ELIMIT;
-    EPNET_REQUIRE(gc >= 7 && gc <= 16);
-    EPNET_REQUIRE(pred_boxes3d && (gt_boxes3d || g == 0) && (thresholds || nt == 0) && workspace && scene_stats);
-    if (seg_counts) {
-        EPNET_REQUIRE(n == 0 || (seg_result && rpn_cls_label));
-    } else {
-        EPNET_REQUIRE(!seg_result && !rpn_cls_label);
-    }
-    const EvalPlan p = eval_plan(b, m, g);
-    if (workspace_bytes < p.bytes) return EPNET_ENOMEM;
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    long long *seg_partial = (long long *)(ws + p.off_seg);
-    float *gt_max = (float *)(ws + p.off_gt_max);
-    float *mat = (float *)(ws + p.off_mat);
-    EvalThresholds thr;
-    for (int t = 0; t < kEvalMaxT; ++t) thr.v[t] = t < nt ? thresholds[t] : 0.f;
-    int rc;
-    if (g > 0) {
-        hipLaunchKernelGGL(eval_iou_kernel, dim3(g, roi_boxes3d ? 2 : 1, b), dim3(256), 0, s, m, g, gc, pred_boxes3d, roi_boxes3d,
-                           gt_boxes3d, gt_max, pred_max_iou ? mat : (float *)nullptr);
-        rc = check_launch("eval_recall iou");
-        if (rc) return rc;
-    }
-    int seg_blocks = 0;
-    const long long total = (long long)b * n;
-    if (seg_counts && total > 0) {
-        seg_blocks = (int)(div_up64(total, 256 * 8) < kEvalSegBlocks ? div_up64(total, 256 * 8) : kEvalSegBlocks);
-        hipLaunchKernelGGL(eval_seg_kernel, dim3(seg_blocks), dim3(256), 0, s, total, seg_result, rpn_cls_label, seg_partial);
-        rc = check_launch("eval_recall seg");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(eval_finish_kernel, dim3(b), dim3(256), 0, s, m, g, gc, nt, thr, roi_boxes3d ? 1 : 0, gt_boxes3d,
-                       (const float *)gt_max, (const float *)mat, (const long long *)seg_partial, seg_blocks, scene_stats,
-                       (long long *)seg_counts, (unsigned long long *)totals, gt_max_pred, gt_max_roi, pred_max_iou);
-    return check_launch("eval_recall finish");
 }

@@ -14,12 +14,13 @@
 //     box covers it, which is what the two nested loops count;
 //   * per-frame partial sums, then one reduction in a fixed order: no atomics, the bits depend on the inputs alone.
 // The rotated intersection is the evaluator's own algorithm in float32, source order (rotate_iou.py:18-261); it is NOT
-// box_overlap of iou3d.hip, which differs on identical, edge-sharing and nested boxes. Its polygon (8 points) and sort keys
+// box_overlap of boxgeom.h, which differs on identical, edge-sharing and nested boxes. Its polygon (8 points) and sort keys
 // live in LDS columns, one per lane: they are indexed at run time and would otherwise go to scratch memory.
 #include <math.h>
 
 #include "common.h"
 #include "cr_cos.h"
+#include "cr_trig.h"
 
 namespace epnet {
 
@@ -34,9 +35,6 @@ constexpr int kDtSlots = kMaxDt / kWave;  // detections per lane: one bit each i
 constexpr int kOvWavesPerFrame = 4;       // waves that share one frame's overlap block
 constexpr int kPolyPts = 8;               // rotate_iou.py:236: intersection_corners holds 16 floats
 constexpr double kNoDetection = -10000000.0;  // eval.py:181
-
-__device__ __forceinline__ float cr_cosf(float x) { return (float)cos((double)x); }
-__device__ __forceinline__ float cr_sinf(float x) { return (float)sin((double)x); }
 
 // rotate_iou.py:205-229
 __device__ __forceinline__ void rbbox_to_corners(float *corners, const float *rbbox) {
@@ -464,8 +462,6 @@ __global__ __launch_bounds__(kWave) void kitti_pr_reduce_kernel(int frames, int 
     }
 }
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 bool fill_combos(Combos &cb, int combos, int num_difficulty, const int *difficulty, const double *min_overlap, const int *num_thresholds,
                  int tstride) {
     for (int c = 0; c < kMaxCombos; ++c) {
@@ -524,7 +520,10 @@ extern "C" int epnet_kitti_match(int frames, int total_gt, int total_dt, int max
 extern "C" size_t epnet_kitti_pr_workspace_bytes(int frames, int combos, int tstride) {
     if (frames <= 0 || combos <= 0 || tstride <= 0 || combos > kMaxCombos || tstride > kMaxThresh) return 0;
     const size_t slots = (size_t)frames * combos * tstride;
-    return align16(slots * 3 * sizeof(int)) + align16(slots * sizeof(double));
+    Carver c;  // the per-frame partial counts (3 ints per slot), then the partial similarities
+    c.take(slots * 3 * sizeof(int));
+    c.take(slots * sizeof(double));
+    return c.off;
 }
 
 extern "C" int epnet_kitti_pr(int frames, int total_gt, int total_dt, int max_gt, int max_dt, int max_dc, int num_difficulty, int combos,
@@ -550,8 +549,10 @@ extern "C" int epnet_kitti_pr(int frames, int total_gt, int total_dt, int max_gt
     if (frames > 0) {
         EPNET_REQUIRE(workspace);
         if (workspace_bytes < epnet_kitti_pr_workspace_bytes(frames, combos, tstride)) return EPNET_ENOMEM;
-        part_cnt = (int *)workspace;
-        part_sim = (double *)((char *)workspace + align16((size_t)frames * combos * tstride * 3 * sizeof(int)));
+        const size_t slots = (size_t)frames * combos * tstride;
+        Carver c;
+        part_cnt = (int *)((char *)workspace + c.take(slots * 3 * sizeof(int)));
+        part_sim = (double *)((char *)workspace + c.take(slots * sizeof(double)));
         hipLaunchKernelGGL(kitti_pr_kernel, dim3(frames, tstride, combos), dim3(kWave), 0, (hipStream_t)stream, frames, total_gt, total_dt,
                            tstride, metric, compute_aos != 0, cb, gt_off, dt_off, dc_off, ov_off, overlaps, dt_score, ignored_gt,
                            ignored_dt, dt_bbox, dc_bbox, gt_alpha, dt_alpha, thresholds, part_cnt, part_sim);

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "cr_trig.h"
 
 namespace epnet {
 
@@ -51,12 +52,12 @@ __device__ __forceinline__ float rp_sign(float v) { return v > 0.f ? 1.0f : v < 
 // ry = sign(ry) * pi - ry on a flip
 __device__ __forceinline__ void rp_augment_box(float *b, float ca, float sa, float scale, float flip) {
     const float kPi = 3.14159265358979323846f;
-    const float beta = (float)atan2((double)b[2], (double)b[0]);
+    const float beta = cr_atan2f(b[2], b[0]);
     const float alpha = ((-rp_sign(beta) * kPi) / 2.0f + beta) + b[6];
     const float x = b[0] * ca + b[2] * (-sa), z = b[0] * sa + b[2] * ca;
     b[0] = x;
     b[2] = z;
-    const float beta2 = (float)atan2((double)z, (double)x);
+    const float beta2 = cr_atan2f(z, x);
     b[6] = ((rp_sign(beta2) * kPi) / 2.0f + alpha) - beta2;
 #pragma unroll
     for (int q = 0; q < 6; ++q) b[q] = b[q] * scale;
@@ -94,7 +95,8 @@ __global__ __launch_bounds__(kRpThreads) void roipool3d_kernel(int pts_num, int 
     const float max_dis = 10.0f;
     const float cy = (float)((double)bottom_y - (double)h / 2.0);
     const float hh = h * 0.5f, hw = w * 0.5f, hl = l * 0.5f;
-    const float cosa = (float)cos((double)angle), sina = (float)sin((double)angle);
+    float cosa, sina;
+    cr_cossinf(angle, cosa, sina);
     const float nsina = -sina;
 
     // phase 1: each wave compacts the hits of its quarter of the cloud
@@ -165,8 +167,7 @@ __global__ __launch_bounds__(kRpThreads) void roipool3d_kernel(int pts_num, int 
             const float ang = tr.aug[roi_id * 3 + 0];
             scale = tr.aug[roi_id * 3 + 1];
             flip = tr.aug[roi_id * 3 + 2];
-            ca = (float)cos((double)ang);
-            sa = (float)sin((double)ang);
+            cr_cossinf(ang, ca, sa);
             rp_augment_box(roi, ca, sa, scale, flip);
             rp_augment_box(gtb, ca, sa, scale, flip);
         }
@@ -174,9 +175,11 @@ __global__ __launch_bounds__(kRpThreads) void roipool3d_kernel(int pts_num, int 
         const float kTwoPi = 6.28318530717958647692f;
         float ry_mod = fmodf(roi[6], kTwoPi);
         if (ry_mod != 0.0f && ry_mod < 0.0f) ry_mod = ry_mod + kTwoPi;  // torch's remainder: the sign of the divisor
-        const float c2 = (float)cos((double)roi[6]), s2 = (float)sin((double)roi[6]);
+        float c2, s2;
+        cr_cossinf(roi[6], c2, s2);
         if (threadIdx.x == 0) {
-            const float cm = (float)cos((double)ry_mod), sm = (float)sin((double)ry_mod);
+            float cm, sm;
+            cr_cossinf(ry_mod, cm, sm);
             const float gx = gtb[0] - roi[0], gy = gtb[1] - roi[1], gz = gtb[2] - roi[2];
             float *go = tr.gt_out + roi_id * 7;
             go[0] = gx * cm + gz * (-sm);

@@ -20,6 +20,7 @@
 // Arithmetic: fp32 in source order without contraction, `/` correctly rounded (the conventions of epnet_kitti_records); the
 // scope test compares (double)coordinate against the double bound.
 #include "common.h"
+#include "cr_trig.h"
 
 namespace epnet {
 namespace scan {
@@ -153,7 +154,7 @@ __device__ __forceinline__ void remove_box_setup(const float *__restrict__ bx, f
     const float h = bx[3];
     s[0] = bx[0]; s[1] = (float)((double)bx[1] - (double)h / 2.0); s[2] = bx[2];
     s[3] = h * 0.5f; s[4] = bx[4] * 0.5f; s[5] = bx[5] * 0.5f;
-    s[6] = (float)cos((double)bx[6]); s[7] = (float)sin((double)bx[6]);
+    cr_cossinf(bx[6], s[6], s[7]);
 }
 
 __device__ __forceinline__ bool in_remove_box(const float *s, float x, float y, float z) {

@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "cr_trig.h"
 
 namespace epnet {
 namespace targets {
@@ -51,7 +52,7 @@ __device__ __forceinline__ void augment_box(const Aug &a, float alpha, float g[7
         const double xd = (double)g[0], zd = (double)g[2];
         g[0] = (float)(xd * a.c - zd * a.s);
         g[2] = (float)(xd * a.s + zd * a.c);
-        const float beta = (float)atan2((double)g[2], (double)g[0]);
+        const float beta = cr_atan2f(g[2], g[0]);
         g[6] = ((sign_of(beta) * kPi) / 2.f + alpha) - beta;
     }
 #pragma unroll
@@ -137,7 +138,8 @@ __global__ __launch_bounds__(kThreads) void rpn_targets_kernel(int n, int g, flo
         }
         const bool real = k < g && b[3] > 0.f && b[4] > 0.f && b[5] > 0.f;   // a degenerate hull labels nothing
         const float cy = b[1] - b[3] / 2.f;
-        const float cosa = (float)cos((double)b[6]), sina = (float)sin((double)b[6]);
+        float cosa, sina;
+        cr_cossinf(b[6], cosa, sina);
         const float hh = b[3] * 0.5f, hw = b[4] * 0.5f, hl = b[5] * 0.5f;
         const float eh = (b[3] + extra2) * 0.5f, ew = (b[4] + extra2) * 0.5f, el = (b[5] + extra2) * 0.5f;
         // a negative extent fails every |.| <= test

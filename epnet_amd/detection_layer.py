@@ -7,7 +7,7 @@ behind the network it thresholds the scores and walks the scenes again: ``inds[k
 indexing (a sync), a sort, an NMS whose mask goes to the host, more indexing, ``.cpu()``. Here ``pool_rois`` is the input
 ``cat`` + one launch of ``epnet_roipool3d_canonical`` (csrc/roipool3d.hip) and ``DetectionLayer`` is the decoding (stock tensor
 ops, or with ``fused_decode=True`` one launch of ``epnet_decode_bbox_target``, csrc/handover.hip), a sigmoid
-and ``epnet_rcnn_detections`` (csrc/iou3d.hip: select, batched rotated NMS with device-side counts, emit). Nothing is read
+and ``epnet_rcnn_detections`` (csrc/detections.hip: select, batched rotated NMS with device-side counts, emit). Nothing is read
 back to the host, so the whole second stage can sit inside a captured HIP graph; the results are padded to M rows per scene
 with a device-side count instead of ragged host arrays.
 """

@@ -5,7 +5,7 @@ Between the detector's outputs and the AP evaluator the reference trims the padd
 ``boxes_iou3d_gpu`` twice per scene, reads ``(gt_max_iou > thresh).sum().item()`` ten times and the RPN segmentation IoU
 once, copies the detections to the host, projects their corners with numpy, and prints a text file per frame that the
 evaluator parses again -- about 25 synchronisations per scene. Here ``eval_batch`` is two library calls,
-``epnet_eval_recall`` (csrc/iou3d.hip) and ``epnet_kitti_records`` (csrc/eval.hip), that leave counters and the records of
+``epnet_eval_recall`` and ``epnet_kitti_records`` (csrc/eval.hip), that leave counters and the records of
 the would-be text lines on the device; ``EvalEpoch`` collects them batch by batch without a synchronisation and reads
 everything back ONCE at the end of the epoch: the ``ret_dict`` entries the reference logs, and the ``dt_annos`` that
 ``kitti_eval.get_official_eval_result`` takes in place of the parsed files.

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._tensor import dev_ptr, need, on_device_of, writes
+from ._tensor import dev_ptr, need, on_device_of, opt_ptr, writes
 
 _F = torch.float32
 
@@ -27,15 +27,6 @@ def _anchor3(anchor_size):
     if len(values) != 3:
         raise RuntimeError("anchor_size must hold 3 numbers")
     return (ctypes.c_float * 3)(*values)
-
-
-def _opt(t, name, dtype, count):
-    """device address of an optional tensor (None -> NULL)"""
-    if t is None:
-        return None
-    p = dev_ptr(t, name, dtype)
-    need(t, count, name)
-    return p
 
 
 @writes("boxes")
@@ -88,8 +79,8 @@ def rpn_handover_gpu(scores, rpn_reg, xyz, loc_scope, loc_bin_size, num_head_bin
     ps, pr, px = dev_ptr(scores, "scores", _F), dev_ptr(rpn_reg, "rpn_reg", _F), dev_ptr(xyz, "xyz", _F)
     pb, pq = dev_ptr(ret_bbox3d, "ret_bbox3d", _F), dev_ptr(ret_scores, "ret_scores", _F)
     need(ret_bbox3d, b * post * 7, "ret_bbox3d"); need(ret_scores, b * post, "ret_scores")
-    outs = [_opt(ret_count, "ret_count", torch.int32, b), _opt(seg_mask, "seg_mask", _F, b * n), _opt(pts_depth, "pts_depth", _F, b * n),
-            _opt(proposals, "proposals", _F, b * n * 7), _opt(order, "order", torch.int64, b * n)]
+    outs = [opt_ptr(ret_count, "ret_count", torch.int32, b), opt_ptr(seg_mask, "seg_mask", _F, b * n), opt_ptr(pts_depth, "pts_depth", _F, b * n),
+            opt_ptr(proposals, "proposals", _F, b * n * 7), opt_ptr(order, "order", torch.int64, b * n)]
     size = _anchor3(anchor_size)
     l = _lib.lib()
     ws_bytes = l.epnet_rpn_handover_workspace_bytes(b, n, int(bool(distance_based)), int(pre_nms_top_n), post)

@@ -11,7 +11,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._tensor import dev_ptr, host_ptr, need, on_device_of, writes
+from ._tensor import dev_ptr, host_ptr, need, on_device_of, opt_ptr, writes
 
 _F = torch.float32
 
@@ -188,15 +188,6 @@ def rcnn_detections_gpu(boxes3d, raw_scores, norm_scores, score_thresh, nms_thre
     return 1
 
 
-def _opt(t, name, dtype, count):
-    """device address of an optional tensor (None -> NULL)"""
-    if t is None:
-        return None
-    p = dev_ptr(t, name, dtype)
-    need(t, count, name)
-    return p
-
-
 @writes("scene_stats", "seg_counts", "totals", "gt_max_pred", "gt_max_roi", "pred_max_iou")
 def eval_recall_gpu(pred_boxes3d, roi_boxes3d, gt_boxes3d, thresholds, seg_result, rpn_cls_label, scene_stats, seg_counts=None,
                     totals=None, gt_max_pred=None, gt_max_roi=None, pred_max_iou=None):
@@ -216,7 +207,7 @@ def eval_recall_gpu(pred_boxes3d, roi_boxes3d, gt_boxes3d, thresholds, seg_resul
     nt = len(thr)
     I, L = torch.int32, torch.int64
     pp = dev_ptr(pred_boxes3d, "pred_boxes3d", _F)
-    pr = _opt(roi_boxes3d, "roi_boxes3d", _F, b * m * 7)
+    pr = opt_ptr(roi_boxes3d, "roi_boxes3d", _F, b * m * 7)
     pg = dev_ptr(gt_boxes3d, "gt_boxes3d", _F)
     n = 0
     ps = pl = None
@@ -227,8 +218,8 @@ def eval_recall_gpu(pred_boxes3d, roi_boxes3d, gt_boxes3d, thresholds, seg_resul
         ps, pl = dev_ptr(seg_result, "seg_result", I), dev_ptr(rpn_cls_label, "rpn_cls_label", I)
     po = dev_ptr(scene_stats, "scene_stats", I)
     need(scene_stats, b * (1 + 2 * nt), "scene_stats")
-    outs = [_opt(seg_counts, "seg_counts", L, 3), _opt(totals, "totals", L, 1 + 2 * nt), _opt(gt_max_pred, "gt_max_pred", _F, b * g),
-            _opt(gt_max_roi, "gt_max_roi", _F, b * g), _opt(pred_max_iou, "pred_max_iou", _F, b * m)]
+    outs = [opt_ptr(seg_counts, "seg_counts", L, 3), opt_ptr(totals, "totals", L, 1 + 2 * nt), opt_ptr(gt_max_pred, "gt_max_pred", _F, b * g),
+            opt_ptr(gt_max_roi, "gt_max_roi", _F, b * g), opt_ptr(pred_max_iou, "pred_max_iou", _F, b * m)]
     l = _lib.lib()
     ws_bytes = l.epnet_eval_recall_workspace_bytes(b, m, g)
     ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=pred_boxes3d.device)
@@ -251,12 +242,12 @@ def kitti_records_gpu(boxes3d, scores, count, P2, img_shape, records, rec_count,
     I = torch.int32
     pb, ps = dev_ptr(boxes3d, "boxes3d", _F), dev_ptr(scores, "scores", _F)
     need(scores, b * m, "scores")
-    pc = _opt(count, "count", I, b)
+    pc = opt_ptr(count, "count", I, b)
     pp, pi = dev_ptr(P2, "P2", _F), dev_ptr(img_shape, "img_shape", I)
     need(P2, b * 12, "P2"); need(img_shape, b * 2, "img_shape")
     pr, pn = dev_ptr(records, "records", torch.float64), dev_ptr(rec_count, "rec_count", I)
     need(records, b * m * 13, "records"); need(rec_count, b, "rec_count")
-    px, pv = _opt(bbox_raw, "bbox_raw", _F, b * m * 4), _opt(valid, "valid", I, b * m)
+    px, pv = opt_ptr(bbox_raw, "bbox_raw", _F, b * m * 4), opt_ptr(valid, "valid", I, b * m)
     with on_device_of(boxes3d) as s:
         _lib.check(_lib.lib().epnet_kitti_records(b, m, pb, ps, pc, pp, pi, pr, pn, px, pv, s), "kitti_records")
     return 1

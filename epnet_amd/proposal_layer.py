@@ -6,7 +6,7 @@ reference. The reference decodes the boxes, sorts the scores and then walks the 
 indexing per distance bin, top-K slices, an NMS whose 5 MB suppression mask goes to the host for a greedy sweep under
 the GIL, more slicing, ``torch.cat`` and a copy into the zero-padded result -- about ten host synchronisations per
 scene. Here the decoding and the sort stay stock tensor ops and everything after them is ``epnet_rpn_proposals``
-(csrc/iou3d.hip): bin compaction in score order, one batched NMS (mask + sweep) over all (scene, bin) groups with the
+(csrc/proposals.hip): bin compaction in score order, one batched NMS (mask + sweep) over all (scene, bin) groups with the
 group sizes read from device memory, and the gather into the padded outputs. Nothing is read back to the host, so the
 layer can sit inside a captured HIP graph. ``ProposalLayer(mode, fused_head=True)`` replaces the stock decoding and sort as
 well: ``forward`` is then one ``epnet_rpn_handover`` call (rpn_handover.py, csrc/handover.hip).

@@ -7,7 +7,7 @@ differs is where the work runs:
 * ``aug_roi_by_noise_torch`` (:220-247) walks every sampled ROI on the host -- up to 10 tries per ROI, each a host
   coin, five tiny torch kernels for the noisy box, a single-pair ``boxes_iou3d_gpu`` and a device->host read of the
   IoU for the loop condition: up to 640 round trips per scene. Here the draws of all tries of all ROIs of the BATCH
-  are tables drawn on the device and ``epnet_aug_roi_by_noise`` (csrc/iou3d.hip) runs the same loop for every ROI in
+  are tables drawn on the device and ``epnet_aug_roi_by_noise`` (csrc/rcnn_targets.hip) runs the same loop for every ROI in
   one launch (``aug_roi_by_noise_batched``); foreground and background ROIs differ only in their try limit.
 * ``sample_rois_for_rcnn`` (:85-189): the ROI x ground-truth IoU of every scene is one fused launch (no torch glue),
   the three ``nonzero`` host syncs per scene become ONE copy of the (B, M) overlap maxima per batch, and the index

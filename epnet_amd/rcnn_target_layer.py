@@ -4,7 +4,7 @@ ProposalTargetLayer.forward with sample_rois_for_rcnn :85-218 and data_augmentat
 ``proposal_target_layer.ProposalTargetLayer`` restates the reference's host random streams draw for draw and therefore reads
 the overlaps back and samples on the host. This module is the sync-free form of the same layer: every random decision comes
 from a table drawn on the device (``draw_sampling_tables``), ``sample_rois`` is ONE call of ``epnet_rcnn_sample_rois``
-(csrc/iou3d.hip: the IoU of all scenes, classes, selection, gather and the noise loop) and ``pool_targets`` ONE launch of
+(csrc/rcnn_targets.hip: the IoU of all scenes, classes, selection, gather and the noise loop) and ``pool_targets`` ONE launch of
 ``epnet_roipool3d_train`` (csrc/roipool3d.hip: pooling, per-ROI augmentation, canonical transformation, labels). Nothing is read
 back, so the whole ``rcnn_online`` step can be queued behind the previous one or captured into one HIP graph.
 

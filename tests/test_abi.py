@@ -56,6 +56,50 @@ def test_argument_validation_without_gpu(hiplib):
     assert hiplib.epnet_three_nn(1, 0, 5, None, None, None, None, None) == 0
 
 
+# Workspace sizes of the box features, recorded from the library BEFORE their plans were rewritten on the shared carver
+# (common.h): callers size and slice their buffers by these numbers, so a refactor must return every one of them unchanged.
+# The models' own shapes (B = 2 / 16, M = 512, G = 20, R = 64 / 128, pre / post 9000 / 512), odd sizes, and the limits
+# beyond which an entry point answers 0.
+WORKSPACE_BYTES = {
+    "epnet_rcnn_sample_rois_workspace_bytes": [
+        ((2, 512, 20, 64), 91152), ((16, 512, 20, 128), 737344), ((1, 1, 1, 1), 96), ((3, 300, 7, 64), 33952),
+        ((2, 4096, 33, 1024), 1163280), ((0, 512, 20, 64), 0), ((65536, 512, 20, 64), 0), ((2, 4097, 20, 64), 0),
+        ((2, 512, 0, 64), 0), ((2, 512, 20, 1025), 0),
+    ],
+    "epnet_rpn_proposals_workspace_bytes": [
+        ((2, 1, 9000, 512), 22824032), ((16, 1, 9000, 512), 182592256), ((2, 0, 9000, 512), 44640032),
+        ((16, 0, 9000, 512), 357120256), ((1, 1, 9000, 100), 11412032), ((1, 0, 9000, 100), 22320032), ((3, 1, 37, 5), 18368),
+        ((1, 1, 0, 0), 272), ((1, 0, 0, 0), 272), ((0, 1, 9000, 512), 0), ((2, 1, -1, 512), 0),
+    ],
+    "epnet_rpn_handover_workspace_bytes": [
+        ((2, 16384, 1, 9000, 512), 24003680), ((16, 16384, 1, 9000, 512), 192029440), ((2, 16384, 0, 9000, 512), 45819680),
+        ((1, 4099, 1, 9000, 100), 11559616), ((3, 333, 0, 37, 5), 62704), ((1, 1, 1, 0, 0), 320), ((0, 16384, 1, 9000, 512), 0),
+        ((32768, 16, 1, 10, 10), 0), ((2, 16385, 1, 9000, 512), 0), ((2, 0, 1, 9000, 512), 0),
+    ],
+    "epnet_rcnn_detections_workspace_bytes": [
+        ((2, 512), 180256), ((16, 512), 1441920), ((1, 100), 12832), ((1, 1), 192), ((3, 65), 25008), ((2, 4096), 5111840),
+        ((0, 512), 0), ((2, 4097), 0), ((65536, 4), 0), ((2, 0), 0),
+    ],
+    "epnet_eval_recall_workspace_bytes": [
+        ((2, 512, 20), 88384), ((16, 512, 20), 664064), ((1, 100, 0), 6144), ((1, 1, 1), 6176), ((3, 65, 7), 11792),
+        ((2, 4096, 33), 1088016), ((0, 512, 20), 0), ((2, 4097, 20), 0), ((65536, 4, 4), 0), ((2, 512, -1), 0),
+    ],
+    "epnet_kitti_pr_workspace_bytes": [
+        ((3769, 6, 41), 18543488), ((50, 3, 41), 123008), ((1, 1, 1), 32), ((7, 16, 64), 143360), ((5, 3, 3), 912),
+        ((0, 3, 41), 0), ((3, 17, 41), 0), ((3, 3, 65), 0), ((3, 0, 41), 0),
+    ],
+    "epnet_nms_workspace_bytes": [
+        ((6300,), 5493600), ((9000,), 10872000), ((512,), 73728), ((1,), 88), ((64,), 5632), ((65,), 6240), ((0,), 0), ((-5,), 0),
+    ],
+}
+
+
+@pytest.mark.parametrize("name", sorted(WORKSPACE_BYTES))
+def test_box_feature_workspace_sizes_are_pinned(hiplib, name):
+    for args, expect in WORKSPACE_BYTES[name]:
+        assert getattr(hiplib, name)(*args) == expect, (name, args)
+
+
 def test_missing_library_is_loud(monkeypatch, tmp_path):
     from epnet_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

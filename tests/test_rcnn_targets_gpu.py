@@ -1,4 +1,4 @@
-"""The sync-free RCNN training targets on the GPU (epnet_amd/rcnn_target_layer.py over csrc/iou3d.hip and csrc/roipool3d.hip).
+"""The sync-free RCNN training targets on the GPU (epnet_amd/rcnn_target_layer.py over csrc/rcnn_targets.hip and csrc/roipool3d.hip).
 
 Bounds. The selection is compared BIT FOR BIT with the numpy restatement (tests/rcnn_targets_restate.py, held to the existing
 layer in test_rcnn_targets.py) fed with the matrix of ``boxes_iou3d_gpu`` on the same inputs: both sides decide on the same floats,
