@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "dpp.h"
+#include "scene_index_layout.h"
 
 namespace epnet {
 
@@ -99,9 +100,7 @@ __device__ __forceinline__ void block_bbox3(const float *__restrict__ xyz, int n
 // consecutive codes are neighbouring cells. One histogram pass, one scan, one scatter -- ~20x cheaper
 // than a full Morton sort, and buckets of 64 consecutive points are just as compact at the scale of a
 // cell. The order INSIDE a cell is whatever the LDS atomics produce: the layout only decides which work
-// can be skipped, never a result.
-constexpr int kCellBits = 14;
-constexpr int kCells = 1 << kCellBits;
+// can be skipped, never a result. (kCellBits, kCells: scene_index_layout.h)
 
 struct CellGrid {
     float lo[3];
@@ -194,22 +193,7 @@ __device__ __forceinline__ void cell_sort_lds(const float *__restrict__ xyz, int
     __syncthreads();
 }
 
-// ---- scene index: caller scratch shared by FPS, ball query and three_nn of one level ---------------------
-// per scene: the points counting-sorted by cell as float4 (x, y, z, original index; padding = 3e38 / -1),
-// padded to np = a power of two >= 2048, followed (after all scenes) by one box (6 floats) per 64 sorted points
-// ("bucket") and then one box per 256 sorted points ("quad")
-inline int scene_index_np(int n) {
-    int np = 2048;
-    while (np < n) np <<= 1;
-    return np;
-}
-// scenes beyond 16384 points: np floats more per scene at the end -- scratch of the sampling kernel (its running distances
-// in sorted order); nothing else reads or writes that tail
-inline size_t scene_index_bytes(int b, int n) {
-    if (b <= 0 || n < 1024 || n > 65536) return 0;
-    const size_t np = (size_t)scene_index_np(n);
-    return (size_t)b * (np * sizeof(float4) + (np / 64 + np / 256) * 6 * sizeof(float) + (n > 16384 ? np * sizeof(float) : 0));
-}
+// ---- scene index (layout: scene_index_layout.h): the sampling kernel's scratch behind a scene of more than 16384 points
 inline float *scene_index_sampling_scratch(int b, int n, void *index) {
     const size_t np = (size_t)scene_index_np(n);
     return (float *)((char *)index + (size_t)b * (np * sizeof(float4) + (np / 64 + np / 256) * 6 * sizeof(float)));

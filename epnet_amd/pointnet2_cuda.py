@@ -9,7 +9,7 @@ ABI in libepnet_hip.so. Failures raise RuntimeError; the reference prints and ex
 import torch
 
 from . import _lib
-from ._tensor import ROWS16, dev_ptr, dev_ptr16, need, on_device_of, writes
+from ._tensor import ROWS16, dev_ptr, dev_ptr16, need, on_device_of, opt_ptr, writes
 
 _F, _I = torch.float32, torch.int32
 
@@ -235,6 +235,14 @@ def furthest_point_sampling_indexed_wrapper(b, n, m, points, index, temp, idx):
     return 1
 
 
+def _chain_args(b, n, points, prefix_in, prefix_out):
+    """what the sample_centres wrappers share: the optional prefix pointers, and the running distances (kept alive by the caller
+    until its launch is queued) where the sampling kernels need them in memory"""
+    pin, pout = opt_ptr(prefix_in, "prefix_in", _I, b), opt_ptr(prefix_out, "prefix_out", _I, b)
+    temp = None if 64 <= n <= 16384 else torch.full((b, n), 1e10, dtype=_F, device=points.device)
+    return pin, pout, temp, None if temp is None else temp.data_ptr()
+
+
 @writes("idx", "new_xyz", "prefix_out")
 def sample_centres_wrapper(b, n, m, points, index, idx, new_xyz, prefix_in=None, prefix_out=None, prefix_cap=0):
     """furthest_point_sampling from a fresh state + gather of the selected rows: idx (B,M) and new_xyz (B,M,3).
@@ -250,18 +258,11 @@ def sample_centres_wrapper(b, n, m, points, index, idx, new_xyz, prefix_in=None,
     elif prefix_in is None and prefix_out is None:
         raise RuntimeError("new_xyz may be None only with prefix_in / prefix_out (epnet_sample_centres_chain)")
     px, nb = _index_args(index, points)
-    temp = None if 64 <= n <= 16384 else torch.full((b, n), 1e10, dtype=_F, device=points.device)
-    pt = None if temp is None else temp.data_ptr()
+    pin, pout, temp, pt = _chain_args(b, n, points, prefix_in, prefix_out)
     with on_device_of(points) as s:
         if prefix_in is None and prefix_out is None:
             _lib.check(_lib.lib().epnet_sample_centres(b, n, m, pp, px, nb, pt, pi, pn, s), "sample_centres")
         else:
-            pin = dev_ptr(prefix_in, "prefix_in", _I) if prefix_in is not None else None
-            pout = dev_ptr(prefix_out, "prefix_out", _I) if prefix_out is not None else None
-            if prefix_in is not None:
-                need(prefix_in, b, "prefix_in")
-            if prefix_out is not None:
-                need(prefix_out, b, "prefix_out")
             _lib.check(_lib.lib().epnet_sample_centres_chain(b, n, m, pp, px, nb, pt, pi, pn, pin, pout, int(prefix_cap), s),
                        "sample_centres")
     return 1
@@ -278,14 +279,7 @@ def sample_centres_index_wrapper(b, n, m, points, index, idx, new_xyz, next_inde
     nx, nnb = _index_args(next_index, points)
     if nx is None:
         raise RuntimeError("sample_centres_index_wrapper needs the next level's index buffer")
-    pin = dev_ptr(prefix_in, "prefix_in", _I) if prefix_in is not None else None
-    pout = dev_ptr(prefix_out, "prefix_out", _I) if prefix_out is not None else None
-    if prefix_in is not None:
-        need(prefix_in, b, "prefix_in")
-    if prefix_out is not None:
-        need(prefix_out, b, "prefix_out")
-    temp = None if 64 <= n <= 16384 else torch.full((b, n), 1e10, dtype=_F, device=points.device)
-    pt = None if temp is None else temp.data_ptr()
+    pin, pout, temp, pt = _chain_args(b, n, points, prefix_in, prefix_out)
     with on_device_of(points) as s:
         _lib.check(_lib.lib().epnet_sample_centres_chain_index(b, n, m, pp, px, nb, pt, pi, pn, pin, pout, int(prefix_cap), nx, nnb, s),
                    "sample_centres_index")
