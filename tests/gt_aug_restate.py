@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+import box_faces as bf
 import scan_restate as rs
 
 F = np.float32
@@ -185,18 +186,9 @@ def object_points(db, placed, e):
 
 # ---- the sampling ---------------------------------------------------------------------------------------------------------------
 def pts_in_box(rect, box):
-    """pt_in_box3d as epnet_roipool3d evaluates it: rect (P,3) float32, box (7) float32 -> (P) bool"""
-    box = np.asarray(box, F)
-    cx, cz, h = box[0], box[2], box[3]
-    cy = F(D(box[1]) - D(h) / 2.0)
-    hh, hw, hl = h * F(0.5), box[4] * F(0.5), box[5] * F(0.5)
-    cosa, sina = F(np.cos(D(box[6]))), F(np.sin(D(box[6])))
-    x, y, z = rect[:, 0], rect[:, 1], rect[:, 2]
-    with np.errstate(invalid="ignore"):
-        gate = ~((np.abs(x - cx) > F(10.0)) | (np.abs(y - cy) > hh) | (np.abs(z - cz) > F(10.0)))
-        x_rot = (x - cx) * cosa + (z - cz) * (-sina)
-        z_rot = (x - cx) * sina + (z - cz) * cosa
-        return gate & (x_rot >= -hl) & (x_rot <= hl) & (z_rot >= -hw) & (z_rot <= hw)
+    """pt_in_box3d as epnet_roipool3d evaluates it: rect (P,3) float32, box (7) float32 -> (P) bool (box_faces.membership32, the
+    one statement of the predicate)"""
+    return bf.membership32(rect, box)[0]
 
 
 def project(xyz, P2):

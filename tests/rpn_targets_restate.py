@@ -68,6 +68,27 @@ def labels(pts, gt, extra_width=0.2):
     return cls, reg, dist
 
 
+def labels32(pts, gt, extra_width=0.2):
+    """the kernel's documented definition (csrc/targets.hip), on box_faces.membership32: float32 in source order about the centre
+    (x, y - h / 2 in float32, z), no 10 m gate, the enlarged box (h, w, l + 2e) about the same centre, a box with an extent that is
+    not positive labels nothing, the last box decides, regression rows are centre - point as written
+    -> cls (N) int32, reg (N,7) float32"""
+    import box_faces as bf
+    pts, gt = np.asarray(pts, F).reshape(-1, 3), np.asarray(gt, F).reshape(-1, 7)
+    cls, reg = np.zeros(len(pts), np.int32), np.zeros((len(pts), 7), F)
+    for b in gt:
+        if not (b[3] > 0 and b[4] > 0 and b[5] > 0):
+            continue
+        cy = b[1] - b[3] / F(2)
+        in_b = bf.membership32(pts, b, 0.0, gate=False, cy=cy)[0]
+        in_e = bf.membership32(pts, b, extra_width, gate=False, cy=cy)[0]
+        cls[in_e] = np.where(in_b[in_e], 1, -1)
+        with np.errstate(invalid="ignore"):
+            reg[in_b, 0:3] = np.array([b[0], cy, b[2]], F) - pts[in_b]
+        reg[in_b, 3:7] = b[3:7]
+    return cls, reg
+
+
 def targets(pts, gt, alpha=None, aug=None, extra_width=0.2):
     """a batch: pts (B,N,3), gt (B,G,7), alpha (B,G), aug (B,4) or None -> (pts_out, gt_out, cls, reg, face_distance)"""
     pts, gt = np.asarray(pts, F), np.asarray(gt, F)
