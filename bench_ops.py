@@ -958,12 +958,42 @@ def image_head_rows(args, timeit_pair):
             return int(top)
 
         shape = {"B": bsz, "N": n, "H": h, "W": w, "C": cfg.img_channels[1:], "R": cfg.deconv_reduce, "q": quarter}
+        if args.amp != "off":
+            # --amp: the dense lines under torch.autocast on 16-bit maps against the 16-bit points head on the same maps; the
+            # float32 points head (on the same values as float32) beside them for the record
+            low = torch.float16 if args.amp == "fp16" else torch.bfloat16
+            maps32, maps = [m.to(low).float() for m in maps], [m.to(low) for m in maps]
+            assert li_fusion.supports_image_head_at_points(deconvs, conv, bn, maps, rows16=True)
+            dense32 = dense
+
+            def dense():
+                with torch.autocast("cuda", low):
+                    return dense32()
+
+            def points32():
+                return li_fusion.image_head_at_points(maps32, packed, xy)
         if args.image_head_side != "both":
             fn = points if args.image_head_side == "points" else dense
             for _ in range(args.reps):
                 fn()
             torch.cuda.synchronize()
             print(json.dumps({"op": "image_head/%s_alone" % args.image_head_side, "shape": shape, "calls": args.reps}), flush=True)
+            continue
+        if args.amp != "off":
+            diff = float((dense().float() - points().float()).abs().max())
+            diff32 = float((points32() - points().float()).abs().max())
+            peak_d, peak_p, peak_p32 = peak(dense), peak(points), peak(points32)
+            (d1, p1), (d2, p2) = timeit_pair(dense, points), timeit_pair(dense, points)
+            (f1, _), (f2, _) = timeit_pair(points32, points), timeit_pair(points32, points)
+            spread = abs(d1 - d2)
+            faster = p1 < d1 and p2 < d2 and min(d1 - p1, d2 - p2) > spread
+            print(json.dumps({"op": "image_head16", "amp": args.amp, "shape": shape, "ms_dense_autocast": [round(d1, 4), round(d2, 4)],
+                              "ms_points16": [round(p1, 4), round(p2, 4)], "ms_points_f32": [round(f1, 4), round(f2, 4)],
+                              "dense_spread_ms": round(spread, 4), "points16_is_faster": bool(faster), "peak_bytes_dense_autocast": peak_d,
+                              "peak_bytes_points16": peak_p, "peak_bytes_points_f32": peak_p32, "max_abs_diff_dense_points16": diff,
+                              "max_abs_diff_points_f32_points16": diff32, "reps": args.reps}), flush=True)
+            del maps, maps32, xy
+            torch.cuda.empty_cache()
             continue
         diff = float((dense() - points()).abs().max())
         peak_d, peak_p = peak(dense), peak(points)
@@ -984,6 +1014,9 @@ def main():
                     help="only the two-stream backbone's image head: the dense lines against li_fusion.image_head_at_points")
     ap.add_argument("--image-head-side", default="both", choices=["both", "points", "dense"],
                     help="with --image-head-only: run one side alone, --reps calls per size (for a kernel trace)")
+    ap.add_argument("--amp", default="off", choices=["off", "bf16", "fp16"],
+                    help="with --image-head-only: 16-bit maps -- the dense lines under torch.autocast against the 16-bit points head "
+                         "(li_fusion.image_head_at_points on float16 / bfloat16 maps), the float32 points head beside them")
     ap.add_argument("--image-head-scenes", default="1,2,16", help="with --image-head-only: the batch sizes, comma separated")
     ap.add_argument("--gt-aug-only", action="store_true",
                     help="only GT-database augmentation: gt_aug_layer.prepare_scans_gt_aug against scan_layer.prepare_scans on the same scans")

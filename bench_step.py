@@ -51,7 +51,7 @@ RCNN_MLPS = [[128, 128, 128], [128, 128, 256], [256, 256, 512]]
 PROPOSALS_DEFAULT = "composed"       # --proposals: the stock decoding + sort in front of epnet_rpn_proposals
 
 
-def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder", image_head="dense"):
+def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder", image_head="dense", image_head_rows16=False):
     """the two-stage model; scale > 1 divides the pyramid's point counts (small test configurations); image: the
     two-stream backbone with LI-Fusion (configs 3 / 4) instead of the point stream alone; loss: "placeholder" (sums of squares),
     "reference" (the real losses, fused: epnet_amd.loss_utils) or "composed" (the real losses as the reference composes them from
@@ -93,7 +93,8 @@ def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="plac
             super().__init__()
             # lib/net/pointnet2_msg.py:126-259 (rpn.py:19: input_channels = 0, the yaml has USE_INTENSITY False)
             self.backbone = rpn_backbone.Pointnet2MSG(input_channels=0, config=rpn_backbone.BackboneConfig(li_fusion=image),
-                                                      sampler=sampler, scale=scale, pyramid=PYRAMID, image_head=image_head)
+                                                      sampler=sampler, scale=scale, pyramid=PYRAMID, image_head=image_head,
+                                                      image_head_rows16=image_head_rows16)
             self.two_stream = image
             self.rpn_cls = nn.Sequential(pt_utils.Conv1d(128, 128, bn=True), pt_utils.Conv1d(128, 1, activation=None))
             self.rpn_reg = nn.Sequential(pt_utils.Conv1d(128, 128, bn=True), pt_utils.Conv1d(128, rpn_channels, activation=None))
@@ -192,9 +193,15 @@ def synthetic_batch(batch, points, seed, device):
 def infer(args, model, proposal_layer, xyz, image=None, xy=None):
     """inference latency, eager launches against one HIP-graph replay: the RPN stage and, with --two-stage, the whole detector;
     image / xy: the two-stream backbone's inputs (--image)"""
+    import contextlib
     import torch
     model.eval()
     two_stream = {"image": True, "image_head": args.image_head} if image is not None else {}
+    # --amp: backbone, heads and the RCNN stage under torch.autocast; the proposal / detection layers and pool_rois make their own
+    # float32 region. No loss, so float16 needs no scale here
+    amp = (lambda: contextlib.nullcontext()) if args.amp == "off" else (
+        lambda: torch.autocast("cuda", torch.float16 if args.amp == "fp16" else torch.bfloat16))
+    dtype = "f32" if args.amp == "off" else "%s autocast (parameters f32)" % args.amp
     if image is not None:
         # the image stream's convolutions: at 2 scenes the dense library's default choice sums in an order that changes from run to
         # run, so two EAGER runs of the RPN stage already differ (graph_equals_eager false with either head, measured); as for the
@@ -210,7 +217,7 @@ def infer(args, model, proposal_layer, xyz, image=None, xy=None):
         return feats, cls[:, :, 0].contiguous(), reg
 
     def stage():
-        with torch.no_grad():
+        with torch.no_grad(), amp():
             _, scores, reg = rpn()
             return proposal_layer(scores, reg, xyz)
 
@@ -242,7 +249,7 @@ def infer(args, model, proposal_layer, xyz, image=None, xy=None):
     ms_eager, ms_graph, same, _ = eager_and_graph(stage)
     print(json.dumps({"metric": "RPN-stage inference latency (backbone + heads + proposal layer, eval mode)", "scenes": args.batch,
                       "points_per_scene": args.points, "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3),
-                      "graph_equals_eager": bool(same), "proposals": args.proposals, "dtype": "f32", "data": "synthetic",
+                      "graph_equals_eager": bool(same), "proposals": args.proposals, "dtype": dtype, "data": "synthetic",
                       **two_stream}), flush=True)
     if not args.two_stage:
         return
@@ -258,7 +265,7 @@ def infer(args, model, proposal_layer, xyz, image=None, xy=None):
     torch.backends.cudnn.deterministic = True
 
     def detector():
-        with torch.no_grad():
+        with torch.no_grad(), amp():
             feats, scores, reg = rpn()
             if fused:                                                            # point_rcnn.py:44-52 in one call
                 from epnet_amd import rpn_handover
@@ -278,7 +285,7 @@ def infer(args, model, proposal_layer, xyz, image=None, xy=None):
     print(json.dumps({"metric": "two-stage inference latency (RPN stage + ROI pooling + RCNN stage + detections, eval mode)",
                       "scenes": args.batch, "points_per_scene": args.points, "rois_per_scene": int(out[0].shape[1]),
                       "ms_eager": round(ms_eager, 3), "ms_hip_graph": round(ms_graph, 3), "graph_equals_eager": bool(same),
-                      "detections": counts, "dense_layers_deterministic": True, "proposals": args.proposals, "dtype": "f32",
+                      "detections": counts, "dense_layers_deterministic": True, "proposals": args.proposals, "dtype": dtype,
                       "data": "synthetic", **two_stream}), flush=True)
 
 
@@ -331,7 +338,8 @@ def main():
                     help="bf16: forward under torch.autocast('cuda', torch.bfloat16) -- dense layers and this package's SA / FP operators on "
                          "bfloat16 rows, parameters and their gradients float32. fp16: the same under torch.float16 with dynamic loss "
                          "scaling inside the optimiser step (--optimizer fused only: FusedAdamOneCycle(loss_scale='dynamic'), the loss "
-                         "goes through scale_loss)")
+                         "goes through scale_loss). With --infer: backbone, heads and RCNN stage under that autocast (no loss scale "
+                         "involved), --image-head points on the 16-bit MFMA head (image_head_rows16=True)")
     ap.add_argument("--loss-scale", default="off", choices=["off", "guard"],
                     help="guard: with --optimizer fused under --amp off / bf16, a static loss scale of 1.0 -- the step is skipped on the "
                          "device when a gradient is not finite (--amp fp16 brings its own dynamic scale)")
@@ -347,7 +355,7 @@ def main():
         ap.error("--gt-aug belongs to the point-only loader: --rpn-only --inputs raw, without --image")
     if args.inputs == "raw" and (not args.rpn_only or args.image or args.infer):
         ap.error("--inputs raw starts the point-stream RPN step (--rpn-only, without --image) from raw scans")
-    if (args.amp == "fp16" or args.loss_scale == "guard") and (args.optimizer != "fused" or args.infer):
+    if ((args.amp == "fp16" and not args.infer) or args.loss_scale == "guard") and (args.optimizer != "fused" or args.infer):
         ap.error("--amp fp16 and --loss-scale guard are the fused optimiser's loss scaling: pass --optimizer fused")
     if args.amp == "fp16" and args.loss_scale == "guard":
         ap.error("--amp fp16 scales dynamically; --loss-scale guard belongs to --amp off / bf16")
@@ -381,7 +389,8 @@ def main():
             dist.init_process_group(backend)
     torch.manual_seed(1 + rank)
     np.random.seed(1 + rank)
-    model = build_model(image=args.image, sampler=args.sampler, loss=args.loss, image_head=args.image_head).to(device)
+    model = build_model(image=args.image, sampler=args.sampler, loss=args.loss, image_head=args.image_head,
+                        image_head_rows16=args.image_head == "points" and args.amp != "off").to(device)
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local], find_unused_parameters=False)
     total_steps = args.warmup + args.steps + 8                         # the instrumented pass takes up to 5 more

@@ -19,6 +19,9 @@
 //      relu(shift + wf . d), one lane per (tap, output channel), written to val (tap id, q). The grid is the shape's upper
 //      bound on the tile count; workgroups beyond the data's count leave at once.
 //   4. ih_blend_kernel: one lane per (point, channel), the four taps in the sampler's fixed order.
+//
+// Float16 / bfloat16 maps (epnet_image_head_points_h) take the same steps on 16-bit copies with the two products on MFMA:
+// imghead16.h, included below; steps 2 is shared, the float32 kernels here are untouched by it.
 #include "common.h"
 #include "taps.h"
 
@@ -329,6 +332,8 @@ static int ih_layout(int b, int n, int h, int w, int levels, const int *chans, c
 
 }  // namespace epnet
 
+#include "imghead16.h"
+
 using namespace epnet;
 
 extern "C" size_t epnet_image_head_points_workspace_bytes(int b, int n, int h, int w, int levels, const int *chans,
@@ -402,4 +407,33 @@ extern "C" int epnet_image_head_points(int b, int n, int h, int w, int levels, c
     hipLaunchKernelGGL(ih_blend_kernel, dim3(div_up(n, kIhBlendPoints), b), dim3(kIhThreads),
                        (size_t)kIhBlendPoints * (4 * q + 1) * sizeof(float), s, n, h, w, q, align_corners, xy, val, out);
     return check_launch("image_head_points");
+}
+
+extern "C" size_t epnet_image_head_points_h_workspace_bytes(int b, int n, int h, int w, int levels, const int *chans,
+                                                            const int *kernels, const int *reduce, int q) {
+    IhLayout16 lay;
+    if (ih_layout16(b, n, h, w, levels, chans, kernels, reduce, q, lay) != EPNET_OK || b == 0 || n == 0) return 0;
+    return lay.total;
+}
+
+extern "C" int epnet_image_head_points_h(int b, int n, int h, int w, int levels, const int *chans, const int *kernels,
+                                         const int *reduce, int dtype, const void *const *maps, const void *const *weights16, int q,
+                                         const void *wf16, const float *shift, const float *xy, int align_corners, void *out,
+                                         void *workspace, size_t workspace_bytes, epnet_stream_t stream) {
+    IhLayout16 lay;
+    const int rc = ih_layout16(b, n, h, w, levels, chans, kernels, reduce, q, lay);
+    if (rc != EPNET_OK) return rc;
+    EPNET_REQUIRE(dtype == EPNET_F16 || dtype == EPNET_BF16);
+    if (b == 0 || n == 0) return EPNET_OK;
+    EPNET_REQUIRE(maps && weights16 && wf16 && shift && xy && out);
+    // maps and out: any 2-byte aligned address; the packs are read with 16-byte loads
+    EPNET_REQUIRE(((uintptr_t)wf16 & 15) == 0 && ((uintptr_t)out & 1) == 0);
+    for (int l = 0; l < levels; ++l) EPNET_REQUIRE(maps[l] && weights16[l] && ((uintptr_t)maps[l] & 1) == 0 && ((uintptr_t)weights16[l] & 15) == 0);
+    if (!workspace || workspace_bytes < lay.total) return EPNET_ENOMEM;
+    EPNET_REQUIRE(((uintptr_t)workspace & 15) == 0);
+    if (dtype == EPNET_F16)
+        return ih_launch16<EPNET_F16>(b, n, h, w, levels, chans, kernels, reduce, lay, maps, weights16, q, wf16, shift, xy, align_corners,
+                                      out, (char *)workspace, (hipStream_t)stream);
+    return ih_launch16<EPNET_BF16>(b, n, h, w, levels, chans, kernels, reduce, lay, maps, weights16, q, wf16, shift, xy, align_corners,
+                                   out, (char *)workspace, (hipStream_t)stream);
 }

@@ -13,13 +13,14 @@ float32 kernel on the upcast map, the result rounded once to the map's type; xy 
 
 For inference, ``image_head_at_points`` evaluates the backbone's whole image head -- DeConv x 4, concatenation, 1x1 convolution,
 eval-mode batch norm, ReLU, then this sampler (reference :237-246) -- under the bilinear taps of the points only, from weights
-that ``pack_image_head`` folds once (float32 maps, not differentiable).
+that ``pack_image_head`` folds once (not differentiable). Float32 maps run the float32 kernels; maps that are all
+float16 or all bfloat16 run the MFMA kernels on 16-bit copies and the pack's ``rows16(dtype)`` weights.
 """
 import torch
 from torch.autograd import Function
 
 from . import pointnet2_cuda as _ext
-from ._tensor import as_f32, is_rows16
+from ._tensor import ROWS16, as_f32, is_rows16
 
 
 class _FeatureGather(Function):
@@ -103,10 +104,34 @@ class PackedImageHead:
     tap phase's slice is contiguous --, ``wf`` (q, sum R) = the 1x1 weight times the batch-norm scale, ``shift`` (q) = the
     batch-norm shift + scale * (1x1 bias + the 1x1 image of the deconvolution biases); folded in float64, rounded once"""
 
-    __slots__ = ("weights", "wf", "shift", "chans", "kernels", "reduce", "q", "stamp")
+    __slots__ = ("weights", "wf", "shift", "chans", "kernels", "reduce", "q", "stamp", "_rows16")
 
     def is_current(self, deconvs, conv, bn):
         return self.stamp == _head_stamp(deconvs, conv, bn)
+
+    def rows16(self, dtype):
+        """(weights16, wf16) for float16 / bfloat16 maps: the float32 pack rounded once to `dtype`, zero padded and laid out in
+        the B-fragment order include/epnet_ops.h documents for epnet_image_head_points_h. Built on first use, once per dtype;
+        it lives and dies with this pack"""
+        if dtype not in ROWS16:
+            raise RuntimeError("PackedImageHead.rows16: torch.float16 or torch.bfloat16, got %s" % (dtype,))
+        if dtype not in self._rows16:
+            self._rows16[dtype] = ([_fragment_order(wd.to(dtype)) for wd in self.weights],
+                                   _fragment_order(self.wf.to(dtype).t().contiguous()))
+        return self._rows16[dtype]
+
+
+def _fragment_order(w):
+    """(..., K, N) -> (..., Np / 16, Kp / 32, 4, 16, 8), element [nb][ks][kq][col][e] = w[..., 32 ks + 8 kq + e, 16 nb + col], zeros
+    where K or N is padded: a wave's B fragment of v_mfma_f32_16x16x32 is 1 KB contiguous, a lane's 8 K-consecutive values 16 bytes"""
+    k, n = w.shape[-2], w.shape[-1]
+    kp, np_ = (k + 31) // 32 * 32, (n + 15) // 16 * 16
+    lead = tuple(w.shape[:-2])
+    padded = w.new_zeros(lead + (kp, np_))
+    padded[..., :k, :n] = w
+    at = len(lead)
+    frag = padded.reshape(lead + (kp // 32, 4, 8, np_ // 16, 16))       # [ks][kq][e][nb][col]
+    return frag.permute(*range(at), at + 3, at + 0, at + 1, at + 4, at + 2).contiguous()
 
 
 def pack_image_head(deconvs, conv, bn, previous=None):
@@ -120,6 +145,7 @@ def pack_image_head(deconvs, conv, bn, previous=None):
         raise RuntimeError("pack_image_head: needs kernel == stride deconvolutions with kernels in %r, a 1x1 convolution over their "
                            "concatenation and a BatchNorm2d with running statistics" % (_HEAD_KERNELS,))
     p = PackedImageHead()
+    p._rows16 = {}
     p.stamp = _head_stamp(deconvs, conv, bn)
     with torch.no_grad():
         p.chans = [d.in_channels for d in deconvs]
@@ -141,17 +167,25 @@ def pack_image_head(deconvs, conv, bn, previous=None):
     return p
 
 
-def supports_image_head_at_points(deconvs, conv, bn, maps):
+def supports_image_head_at_points(deconvs, conv, bn, maps, rows16=False):
     """True when ``image_head_at_points`` can stand in for the dense head: every DeConv is the plain kernel == stride form with
     a kernel in {1, 2, 4, 8, 16}, a 1x1 convolution and a BatchNorm2d follow, the maps are float32 (B, C_l, H / k_l, W / k_l) of
-    one full size (H, W) that is a multiple of the largest kernel, and the widths are within the kernels' limits"""
+    one full size (H, W) that is a multiple of the largest kernel, and the widths are within the kernels' limits. rows16=True:
+    maps that are all float16 or all bfloat16 are accepted as well (the 16-bit rule of DESIGN 4.12)"""
     deconvs, maps = list(deconvs), list(maps)
     if len(maps) != len(deconvs) or not _plain_head(deconvs, conv, bn):
         return False
+    kinds = set(m.dtype for m in maps if isinstance(m, torch.Tensor))
+    if rows16 and len(kinds) == 1 and next(iter(kinds)) in ROWS16:
+        return _supported_shapes(deconvs, maps, next(iter(kinds)))
+    return _supported_shapes(deconvs, maps, torch.float32)
+
+
+def _supported_shapes(deconvs, maps, dtype):
     kmax = max(d.kernel_size[0] for d in deconvs)
     sizes = set()
     for d, m in zip(deconvs, maps):
-        if not (isinstance(m, torch.Tensor) and m.dim() == 4 and m.dtype == torch.float32 and m.shape[1] == d.in_channels):
+        if not (isinstance(m, torch.Tensor) and m.dim() == 4 and m.dtype == dtype and m.shape[1] == d.in_channels):
             return False
         sizes.add((m.shape[0], m.shape[2] * d.kernel_size[0], m.shape[3] * d.kernel_size[0]))
     if len(sizes) != 1:
@@ -161,9 +195,11 @@ def supports_image_head_at_points(deconvs, conv, bn, maps):
 
 
 def image_head_at_points(maps, packed, xy, align_corners=True):
-    """maps: the float32 image maps F_l (B, C_l, H / k_l, W / k_l) the DeConv layers would upsample; packed: pack_image_head(...);
-    xy (B, N, 2) in [-1, 1] -> (B, q, N) float32 = Feature_Gather(relu(bn(conv(cat(DeConv_l(F_l))))), xy) of the eval-mode modules,
-    evaluated under the bilinear taps only. Inference only: not differentiable, the result carries no graph."""
+    """maps: the image maps F_l (B, C_l, H / k_l, W / k_l) the DeConv layers would upsample, all float32 or all float16 or all
+    bfloat16; packed: pack_image_head(...); xy (B, N, 2) float32 in [-1, 1] -> (B, q, N) of the maps' type =
+    Feature_Gather(relu(bn(conv(cat(DeConv_l(F_l))))), xy) of the eval-mode modules, evaluated under the bilinear taps only (16-bit
+    maps: by the rule of DESIGN 4.12, weights and the deconvolutions' result rounded to the type). Inference only: not
+    differentiable, the result carries no graph."""
     maps = [m.detach().contiguous() for m in maps]
     xy = xy.detach().contiguous()
     b, n = xy.shape[0], xy.shape[1]
@@ -174,6 +210,16 @@ def image_head_at_points(maps, packed, xy, align_corners=True):
             raise RuntimeError("image_head_at_points: map of shape %r, expected %r" % (tuple(m.shape), (b, c, h // k, w // k)))
     if xy.is_cuda and packed.wf.device != xy.device:
         raise RuntimeError("image_head_at_points: the pack lives on %s, xy on %s" % (packed.wf.device, xy.device))
+    kinds = set(m.dtype for m in maps)
+    if len(kinds) != 1:
+        raise RuntimeError("image_head_at_points: maps of one type, got %s" % sorted(str(k) for k in kinds))
+    dtype = next(iter(kinds))
+    if dtype in ROWS16:
+        weights16, wf16 = packed.rows16(dtype)
+        out = torch.empty((b, packed.q, n), dtype=dtype, device=xy.device)
+        _ext.image_head_points_h_wrapper(b, n, h, w, packed.chans, packed.kernels, packed.reduce, maps, weights16, packed.q, wf16,
+                                         packed.shift, xy, align_corners, out)
+        return out
     out = torch.empty((b, packed.q, n), dtype=torch.float32, device=xy.device)
     _ext.image_head_points_wrapper(b, n, h, w, packed.chans, packed.kernels, packed.reduce, maps, packed.weights, packed.q,
                                    packed.wf, packed.shift, xy, align_corners, out)

@@ -631,3 +631,47 @@ def image_head_points_wrapper(b, n, h, w, chans, kernels, reduce, maps, weights,
         _lib.check(l.epnet_image_head_points(b, n, h, w, levels, ac, ak, ar, am, aw, q, pf, ps, px, int(bool(align_corners)), po,
                                              ws.data_ptr(), given, s), "image_head_points")
     return 1
+
+
+def image_head_points_h_workspace_bytes(b, n, h, w, chans, kernels, reduce, q):
+    """scratch of image_head_points_h_wrapper for these shapes (0: empty problem or outside what the kernels support)"""
+    return int(_lib.lib().epnet_image_head_points_h_workspace_bytes(b, n, h, w, len(chans), _int_array(chans), _int_array(kernels),
+                                                                    _int_array(reduce), q))
+
+
+@writes("out")
+def image_head_points_h_wrapper(b, n, h, w, chans, kernels, reduce, maps, weights16, q, wf16, shift, xy, align_corners, out,
+                                workspace=None):
+    """the image head at the points on float16 / bfloat16 maps (include/epnet_ops.h: epnet_image_head_points_h). maps, weights16,
+    wf16 and out share one 16-bit type; the packs are PackedImageHead.rows16(dtype)'s; workspace as image_head_points_wrapper"""
+    import ctypes
+    levels = len(chans)
+    if not (levels == len(kernels) == len(reduce) == len(maps) == len(weights16)):
+        raise RuntimeError("image_head_points_h: one entry per level in chans, kernels, reduce, maps and weights16")
+    dtype = out.dtype if isinstance(out, torch.Tensor) else None
+    pad = lambda v, to: (int(v) + to - 1) // to * to
+    sum_r = sum(int(r) for r in reduce)
+    pm, pw = [], []
+    for l in range(levels):
+        pm.append(dev_ptr16(maps[l], "maps[%d]" % l, dtype))
+        pw.append(dev_ptr16(weights16[l], "weights16[%d]" % l, dtype))
+        need(maps[l], b * chans[l] * (h // kernels[l]) * (w // kernels[l]), "maps[%d]" % l)
+        need(weights16[l], kernels[l] * kernels[l] * pad(chans[l], 32) * pad(reduce[l], 16), "weights16[%d]" % l)
+    pf, po = dev_ptr16(wf16, "wf16", dtype), dev_ptr16(out, "out", dtype)
+    ps, px = dev_ptr(shift, "shift", _F), dev_ptr(xy, "xy", _F)
+    need(wf16, pad(q, 16) * pad(sum_r, 32), "wf16"); need(shift, q, "shift"); need(xy, b * n * 2, "xy"); need(out, b * q * n, "out")
+    l = _lib.lib()
+    ac, ak, ar = _int_array(chans), _int_array(kernels), _int_array(reduce)
+    ws_bytes = int(l.epnet_image_head_points_h_workspace_bytes(b, n, h, w, levels, ac, ak, ar, q))
+    am, aw = (ctypes.c_void_p * levels)(*pm), (ctypes.c_void_p * levels)(*pw)
+    with on_device_of(xy) as s:
+        if workspace is None:
+            ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=xy.device)
+            given = ws_bytes
+        else:
+            ws, given = workspace, workspace.numel()
+            if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != xy.device:
+                raise RuntimeError("image_head_points_h workspace: a contiguous uint8 tensor on the tensors' device")
+        _lib.check(l.epnet_image_head_points_h(b, n, h, w, levels, ac, ak, ar, ROWS16[dtype], am, aw, q, pf, ps, px,
+                                               int(bool(align_corners)), po, ws.data_ptr(), given, s), "image_head_points_h")
+    return 1

@@ -17,7 +17,9 @@ reference was written for torch <= 1.2, which behaved that way) -- the yardstick
 ``image_head``: "dense" (default) = the reference's end of the forward, the full-resolution fusion map sampled at the points;
 "points" = for inference, ``li_fusion.image_head_at_points`` evaluates that head under the bilinear taps only.
 It is taken only in eval mode, on the GPU, on float32 maps (not under autocast), for a supported configuration and when no
-gradient is needed; in every other case "points" runs exactly the dense lines.
+gradient is needed; in every other case "points" runs exactly the dense lines. ``image_head_rows16=True`` (default False)
+lifts the autocast exclusion: under ``torch.autocast`` with maps that are all of the autocast type, the same conditions take
+the 16-bit MFMA form of the head (its rule rounds the weights and the deconvolutions' result to that type).
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -138,14 +140,15 @@ def stock_feature_gather(feature_map, xy):
 
 class Pointnet2MSG(nn.Module):
     def __init__(self, input_channels=0, use_xyz=True, config: BackboneConfig = None, sampler="hip", scale=1, pyramid=True,
-                 image_head="dense"):
+                 image_head="dense", image_head_rows16=False):
         """scale > 1 divides the pyramid's point counts (small test configurations); pyramid: sample all levels up front on
-        a side stream (pointnet2_utils.sample_pyramid); image_head: see the module's docstring"""
+        a side stream (pointnet2_utils.sample_pyramid); image_head, image_head_rows16: see the module's docstring"""
         super().__init__()
         cfg = self.cfg = config or BackboneConfig()
         assert sampler in ("hip", "stock")
         assert image_head in ("dense", "points")
         self.sampler, self.pyramid, self.image_head = sampler, pyramid, image_head
+        self.image_head_rows16 = bool(image_head_rows16)
         self._packed_head = None                   # li_fusion.pack_image_head's result: a cache, not part of the state_dict
         self.SA_modules = nn.ModuleList()
         channel_in, skips = input_channels, [input_channels]
@@ -188,17 +191,21 @@ class Pointnet2MSG(nn.Module):
 
     def _head_at_points(self, maps, xy):
         """the "points" image head when every condition of the module's docstring holds, else None"""
-        if self.image_head != "points" or self.training or not xy.is_cuda or torch.is_autocast_enabled():
+        if self.image_head != "points" or self.training or not xy.is_cuda:
             return None
-        if not all(m.is_cuda and m.dtype == torch.float32 for m in maps):
+        rows16 = torch.is_autocast_enabled()
+        if rows16 and not self.image_head_rows16:
+            return None
+        want = torch.get_autocast_dtype("cuda") if rows16 else torch.float32
+        if not all(m.is_cuda and m.dtype == want for m in maps):
             return None
         if torch.is_grad_enabled() and (any(m.requires_grad for m in maps) or xy.requires_grad or any(
                 p.requires_grad for mod in (self.DeConv, self.image_fusion_conv, self.image_fusion_bn) for p in mod.parameters())):
             return None
-        if not li_fusion.supports_image_head_at_points(self.DeConv, self.image_fusion_conv, self.image_fusion_bn, maps):
+        if not li_fusion.supports_image_head_at_points(self.DeConv, self.image_fusion_conv, self.image_fusion_bn, maps, rows16=rows16):
             return None
         self._packed_head = li_fusion.pack_image_head(self.DeConv, self.image_fusion_conv, self.image_fusion_bn, self._packed_head)
-        return li_fusion.image_head_at_points(maps, self._packed_head, xy)
+        return li_fusion.image_head_at_points(maps, self._packed_head, xy.float() if rows16 else xy)
 
     def forward(self, pointcloud, image=None, xy=None):
         """pointcloud (B,N,3+C), image (B,3,H,W), xy (B,N,2) pixel coordinates -- normalised to [-1,1] IN PLACE, as the

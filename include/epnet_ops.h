@@ -1017,6 +1017,37 @@ int epnet_image_head_points(int b, int n, int h, int w, int levels, const int *c
                             const float *xy, int align_corners, float *out, void *workspace, size_t workspace_bytes,
                             epnet_stream_t stream);
 
+/* The same head on 16-bit maps (torch.autocast inference), on v_mfma_f32_16x16x32_{f16,bf16}. T = dtype = EPNET_F16 or EPNET_BF16;
+ * every map, both packs and out are of type T; shift and xy stay fp32. The rule (it is NOT the "fp32 op on the upcast inputs,
+ * rounded once" rule of the other *_h entries: the weights and the intermediate d are rounded to T, as autocast rounds the
+ * weights and the activations of the dense head):
+ *   out[b, c, n] = round_T( sum over the in-bounds taps (nw, ne, sw, se) of weight_tap * relu(shift[c] + sum_j wf16[c, j] * d16[j](tap)) )
+ *   d16[j](tap)  = round_T( sum_ci wd16_l[Y % k_l, X % k_l, ci, r] * F_l[b, ci, Y / k_l, X / k_l] ),  j = (sum of R before l) + r
+ *   wd16_l = round_T(wd_l), wf16 = round_T(wf) of the fp32 pack above.
+ * Products are exact in fp32 and the sums over ci and j are accumulated in fp32 in the order the MFMA takes (not pinned); the
+ * four taps are blended in fp32 in the fixed order, as above. Every round_T is to nearest even, keeps denormals and overflows to
+ * infinity. Taps, tap weights and the in-bounds rule are those of epnet_feature_gather. No float atomics: a tap's value depends
+ * on its pixel, its scene's maps and the weights alone (each row of an MFMA result depends on its own A row only).
+ * Packed weights, in the MFMA's B-fragment order, with Cp_l = C_l rounded up to 32, Rp_l = R_l rounded up to 16,
+ * SRp = sum R rounded up to 32 and qp = q rounded up to 16:
+ *   weights16[l]: (k_l, k_l, Rp_l / 16, Cp_l / 32, 4, 16, 8) of T, element [py][px][nb][ks][kq][col][e] =
+ *     wd16_l[py, px, ci = 32 ks + 8 kq + e, r = 16 nb + col], an exact zero where ci >= C_l or r >= R_l
+ *   wf16: (qp / 16, SRp / 32, 4, 16, 8) of T, element [qb][ks][kq][col][e] = wf16[c = 16 qb + col, j = 32 ks + 8 kq + e], an exact
+ *     zero where c >= q or j >= sum R
+ * Both 16-byte aligned, else EPNET_EINVAL; maps[l] and out may sit at any 2-byte aligned address.
+ * Workspace, each part rounded up to 256 bytes, in this order: per level the pixel-major copy (b, h / k_l * w / k_l, Cp_l) of T
+ * with the channels C_l .. Cp_l - 1 written as zeros (2 b P_l Cp_l bytes); val (4 b n, q) fp32; the tap order 4 b n int32; the four
+ * tables (256 + 256 + 257 + 257) int32. 16-byte aligned. epnet_image_head_points_h_workspace_bytes is that sum, pure arithmetic,
+ * 0 outside the limits or for an empty problem.
+ * levels + 5 launches and one memset whatever the data, no host synchronisation, no allocation; records into a HIP graph. Limits
+ * and error codes of the fp32 entry, all answered before any launch; an unknown dtype: EPNET_EINVAL. */
+size_t epnet_image_head_points_h_workspace_bytes(int b, int n, int h, int w, int levels, const int *chans, const int *kernels,
+                                                 const int *reduce, int q);
+int epnet_image_head_points_h(int b, int n, int h, int w, int levels, const int *chans, const int *kernels, const int *reduce,
+                              int dtype, const void *const *maps, const void *const *weights16, int q, const void *wf16,
+                              const float *shift, const float *xy, int align_corners, void *out, void *workspace,
+                              size_t workspace_bytes, epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
