@@ -5,7 +5,7 @@ gradient ops, at the shapes of the reference's rcnn_online step (SURVEY.md secti
 median HIP-event time, algorithmic bytes (SURVEY.md 8d formulas) and the resulting GB/s.
 
     python bench_ops.py [--reps 20] [--stage2-only | --loss-only | --targets-only | --optim-only | --scan-only | --gt-aug-only | --handover-only |
-                         --image-head-only]
+                         --image-head-only | --sa-tail-only]
 """
 import argparse
 import json
@@ -1007,6 +1007,77 @@ def image_head_rows(args, timeit_pair):
         torch.cuda.empty_cache()
 
 
+def sa_tail_rows(args, timeit_pair):
+    """the end of every SA level's shared MLP alone, per level and scale of configs 3 / 4 (16384 points per scene, the
+    yaml's widths) and of the RCNN stage's SA stack (100 ROIs per scene): the stock lines -- [batch norm,] ReLU of the unit before the
+    last, then convolution, [batch norm,] ReLU and pool_max -- against pointnet2_utils.sa_tail on the same pre-activation, eval mode
+    under no_grad. Alternating inside one call, median of --reps by HIP events, two passes; "faster" = below the stock side in both
+    passes by more than the stock side's own spread between its passes. share_of_8TBps: (x + y + w bytes) / fused time / 8 TB/s."""
+    import torch
+    import bench_step
+    from epnet_amd import pointnet2_utils as p2u, pytorch_utils as pt_utils, rpn_backbone
+    dev = torch.device("cuda:0")
+    cfg = rpn_backbone.BackboneConfig()
+    rows, cin = [], 0
+    for level in range(len(cfg.npoints)):
+        for scale, (spec, ns) in enumerate(zip(cfg.mlps[level], cfg.nsample[level])):
+            rows.append(("rpn level %d scale %d" % (level + 1, scale + 1), [cin + 3] + list(spec), cfg.use_bn, 1, cfg.npoints[level], ns))
+        cin = sum(m[-1] for m in cfg.mlps[level])
+    cin, rois = 128, 100
+    for level, spec in enumerate(bench_step.RCNN_MLPS):
+        group_all = bench_step.RCNN_NPOINTS[level] is None
+        rows.append(("rcnn level %d" % (level + 1), [cin + 3] + list(spec), False, rois, 1 if group_all else bench_step.RCNN_NPOINTS[level],
+                     bench_step.RCNN_NPOINTS[level - 1] if group_all else bench_step.RCNN_NSAMPLE[level]))
+        cin = spec[-1]
+    g = torch.Generator(device=dev).manual_seed(1)
+    for bsz in [int(v) for v in args.sa_tail_scenes.split(",")]:
+        for name, spec, bn, per_scene, p, ns in rows:
+            torch.manual_seed(0)
+            mlp = pt_utils.SharedMLP(list(spec), bn=bn)
+            with torch.no_grad():
+                for m in mlp.modules():
+                    if isinstance(m, torch.nn.BatchNorm2d):
+                        m.running_mean.normal_(0.0, 0.3)
+                        m.running_var.uniform_(0.5, 2.0)
+            mlp = mlp.to(dev).eval()
+            packed = p2u.pack_sa_tail(mlp)
+            flat = [layer for unit in mlp.children() for layer in unit.children()]
+            tail = flat[len(flat) - packed.replaced:]
+            b, k, c = bsz * per_scene, spec[-2], spec[-1]
+            x = torch.randn((b, k, p, ns), generator=g, device=dev)    # up to 6.7 GB (RCNN level 1 at 16 scenes): drawn on the device
+
+            def stock():
+                with torch.no_grad():
+                    h = x
+                    for layer in tail:
+                        h = layer(h)
+                    return p2u.pool_max(h).squeeze(-1)
+
+            def fused():
+                return p2u.sa_tail(x, packed)
+
+            shape = {"scenes": bsz, "B": b, "K": k, "C": c, "P": p, "S": ns, "bn": bool(bn)}
+            if args.sa_tail_side != "both":
+                fn = fused if args.sa_tail_side == "fused" else stock
+                for _ in range(args.reps):
+                    fn()
+                torch.cuda.synchronize()
+                print(json.dumps({"op": "sa_tail/%s_alone" % args.sa_tail_side, "row": name, "shape": shape, "calls": args.reps}), flush=True)
+                continue
+            y_f, y_s = fused(), stock()          # the fused side first: without a batch norm the stock ReLU works in place on x
+            diff = float((y_f - y_s).abs().max())
+            (s1, f1), (s2, f2) = timeit_pair(stock, fused), timeit_pair(stock, fused)
+            spread = abs(s1 - s2)
+            faster = f1 < s1 and f2 < s2 and min(s1 - f1, s2 - f2) > spread
+            nbytes = 4 * (x.numel() + y_f.numel() + packed.w.numel())
+            print(json.dumps({"op": "sa_tail", "row": name, "shape": shape, "ms_stock": [round(s1, 4), round(s2, 4)],
+                              "ms_fused": [round(f1, 4), round(f2, 4)], "stock_spread_ms": round(spread, 4), "fused_is_faster": bool(faster),
+                              "x_y_w_bytes": nbytes, "share_of_8TBps": round(nbytes / (min(f1, f2) * 1e-3) / 8e12, 4),
+                              "max_abs_diff": diff, "reps": args.reps}), flush=True)
+            del x
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -1018,6 +1089,12 @@ def main():
                     help="with --image-head-only: 16-bit maps -- the dense lines under torch.autocast against the 16-bit points head "
                          "(li_fusion.image_head_at_points on float16 / bfloat16 maps), the float32 points head beside them")
     ap.add_argument("--image-head-scenes", default="1,2,16", help="with --image-head-only: the batch sizes, comma separated")
+    ap.add_argument("--sa-tail-only", action="store_true",
+                    help="only the end of every SA level's shared MLP: the stock convolution / batch norm / ReLU / pool_max lines against "
+                         "pointnet2_utils.sa_tail, per level and scale of configs 3 / 4 and of the RCNN stage")
+    ap.add_argument("--sa-tail-side", default="both", choices=["both", "fused", "stock"],
+                    help="with --sa-tail-only: run one side alone, --reps calls per row (for a kernel trace)")
+    ap.add_argument("--sa-tail-scenes", default="1,2,16", help="with --sa-tail-only: the batch sizes, comma separated")
     ap.add_argument("--gt-aug-only", action="store_true",
                     help="only GT-database augmentation: gt_aug_layer.prepare_scans_gt_aug against scan_layer.prepare_scans on the same scans")
     ap.add_argument("--gt-aug-side", default="both", choices=["both", "fused"],
@@ -1163,6 +1240,8 @@ def main():
         return stage2_infer()
     if args.image_head_only:
         return image_head_rows(args, timeit_pair)
+    if args.sa_tail_only:
+        return sa_tail_rows(args, timeit_pair)
     if args.loss_only:
         return loss_rows(args, report, timeit_pair)
     if args.optim_only:

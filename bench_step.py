@@ -51,13 +51,15 @@ RCNN_MLPS = [[128, 128, 128], [128, 128, 256], [256, 256, 512]]
 PROPOSALS_DEFAULT = "composed"       # --proposals: the stock decoding + sort in front of epnet_rpn_proposals
 
 
-def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder", image_head="dense", image_head_rows16=False):
+def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="placeholder", image_head="dense", image_head_rows16=False,
+                sa_tail="stock"):
     """the two-stage model; scale > 1 divides the pyramid's point counts (small test configurations); image: the
     two-stream backbone with LI-Fusion (configs 3 / 4) instead of the point stream alone; loss: "placeholder" (sums of squares),
     "reference" (the real losses, fused: epnet_amd.loss_utils) or "composed" (the real losses as the reference composes them from
     stock torch calls, with its mask indexing and .item() reads: bench_ops.composed_rpn_loss / composed_rcnn_loss); the real
     losses read the RPN labels from model.rpn_labels = rpn_labels(xyz, gt_boxes3d); image_head: the two-stream backbone's
-    "dense" (default) or "points" (inference: the image head under the bilinear taps only, rpn_backbone.Pointnet2MSG)"""
+    "dense" (default) or "points" (inference: the image head under the bilinear taps only, rpn_backbone.Pointnet2MSG); sa_tail:
+    "stock" (default) or "fused" (inference: every SA level of both stages ends in pointnet2_utils.sa_tail)"""
     import torch
     import torch.nn as nn
     from epnet_amd import pytorch_utils as pt_utils, rpn_backbone
@@ -73,7 +75,8 @@ def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="plac
             cin = 128
             for k in range(len(RCNN_NPOINTS)):
                 self.SA_modules.append(PointnetSAModule(npoint=RCNN_NPOINTS[k], radius=RCNN_RADIUS[k], nsample=RCNN_NSAMPLE[k],
-                                                        mlp=[cin] + RCNN_MLPS[k], use_xyz=True, bn=False))
+                                                        mlp=[cin] + RCNN_MLPS[k], use_xyz=True, bn=False,
+                                                        fused_tail=sa_tail == "fused"))
                 cin = RCNN_MLPS[k][-1]
             self.cls = nn.Sequential(pt_utils.Conv1d(512, 512), pt_utils.Conv1d(512, 512), pt_utils.Conv1d(512, 1, activation=None))
             self.reg = nn.Sequential(pt_utils.Conv1d(512, 512), pt_utils.Conv1d(512, 512), pt_utils.Conv1d(512, 46, activation=None))
@@ -94,7 +97,7 @@ def build_model(scale=1, rpn_channels=76, image=False, sampler="hip", loss="plac
             # lib/net/pointnet2_msg.py:126-259 (rpn.py:19: input_channels = 0, the yaml has USE_INTENSITY False)
             self.backbone = rpn_backbone.Pointnet2MSG(input_channels=0, config=rpn_backbone.BackboneConfig(li_fusion=image),
                                                       sampler=sampler, scale=scale, pyramid=PYRAMID, image_head=image_head,
-                                                      image_head_rows16=image_head_rows16)
+                                                      image_head_rows16=image_head_rows16, sa_tail=sa_tail)
             self.two_stream = image
             self.rpn_cls = nn.Sequential(pt_utils.Conv1d(128, 128, bn=True), pt_utils.Conv1d(128, 1, activation=None))
             self.rpn_reg = nn.Sequential(pt_utils.Conv1d(128, 128, bn=True), pt_utils.Conv1d(128, rpn_channels, activation=None))
@@ -197,6 +200,7 @@ def infer(args, model, proposal_layer, xyz, image=None, xy=None):
     import torch
     model.eval()
     two_stream = {"image": True, "image_head": args.image_head} if image is not None else {}
+    two_stream["sa_tail"] = args.sa_tail
     # --amp: backbone, heads and the RCNN stage under torch.autocast; the proposal / detection layers and pool_rois make their own
     # float32 region. No loss, so float16 needs no scale here
     amp = (lambda: contextlib.nullcontext()) if args.amp == "off" else (
@@ -308,6 +312,10 @@ def main():
                     help="with --image: the end of the image stream -- the full-resolution fusion map sampled at the points (default) "
                          "or, in inference, the head evaluated under the bilinear taps only (li_fusion.image_head_at_points); the "
                          "training steps run the dense lines either way")
+    ap.add_argument("--sa-tail", default="stock", choices=["stock", "fused"],
+                    help="with --infer: the end of every SA level's shared MLP -- the stock conv / batch norm / ReLU / max-pool lines, "
+                         "or the last convolution with its folded batch norm, the ReLU and the pool from one kernel "
+                         "(pointnet2_utils.sa_tail, float32 only); the JSON lines report which one ran")
     ap.add_argument("--rpn-only", action="store_true", help="config 3: forward + backward of backbone + RPN heads only")
     ap.add_argument("--sampler", default="hip", choices=["hip", "stock"],
                     help="point-to-pixel sampler: this package's Feature_Gather or stock torch.gather + grid_sample")
@@ -359,6 +367,8 @@ def main():
         ap.error("--amp fp16 and --loss-scale guard are the fused optimiser's loss scaling: pass --optimizer fused")
     if args.amp == "fp16" and args.loss_scale == "guard":
         ap.error("--amp fp16 scales dynamically; --loss-scale guard belongs to --amp off / bf16")
+    if args.sa_tail != "stock" and not args.infer:
+        ap.error("--sa-tail fused is inference only: pass --infer")
     if args.image_head != "dense" and not args.image:
         ap.error("--image-head belongs to the two-stream backbone: pass --image")
     from epnet_amd import scene_shard
@@ -390,7 +400,7 @@ def main():
     torch.manual_seed(1 + rank)
     np.random.seed(1 + rank)
     model = build_model(image=args.image, sampler=args.sampler, loss=args.loss, image_head=args.image_head,
-                        image_head_rows16=args.image_head == "points" and args.amp != "off").to(device)
+                        image_head_rows16=args.image_head == "points" and args.amp != "off", sa_tail=args.sa_tail).to(device)
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local], find_unused_parameters=False)
     total_steps = args.warmup + args.steps + 8                         # the instrumented pass takes up to 5 more

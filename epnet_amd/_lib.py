@@ -137,6 +137,7 @@ SIGNATURES = {
     "epnet_image_head_points": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "epnet_image_head_points_h_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
     "epnet_image_head_points_h": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "epnet_sa_tail_f32": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "epnet_kitti_thresholds_host": (_i, [_vp, _i64, _i64, _i, _vp, _i, ctypes.POINTER(_i)]),
     "epnet_pts_in_boxes3d_host": (_i, [_vp, _vp, _vp, _i64, _i64]),
     "epnet_roipool3d_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64]),

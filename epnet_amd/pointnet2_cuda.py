@@ -675,3 +675,15 @@ def image_head_points_h_wrapper(b, n, h, w, chans, kernels, reduce, maps, weight
         _lib.check(l.epnet_image_head_points_h(b, n, h, w, levels, ac, ak, ar, ROWS16[dtype], am, aw, q, pf, ps, px,
                                                int(bool(align_corners)), po, ws.data_ptr(), given, s), "image_head_points_h")
     return 1
+
+
+@writes("y")
+def sa_tail_wrapper(b, k, c, p, s, x, w, bias, s_in, t_in, relu_in, y):
+    """the tail of an SA level's shared MLP for inference (include/epnet_ops.h: epnet_sa_tail_f32; not in the reference
+    extension): x (b,k,p,s), w (c,k) with the batch norm folded in, bias (c) or None, s_in / t_in (k) or None -> y (b,c,p)"""
+    px, pw, py = dev_ptr(x, "x", _F), dev_ptr(w, "w", _F), dev_ptr(y, "y", _F)
+    need(x, b * k * p * s, "x"); need(w, c * k, "w"); need(y, b * c * p, "y")
+    pb, ps, pt = opt_ptr(bias, "bias", _F, c), opt_ptr(s_in, "s_in", _F, k), opt_ptr(t_in, "t_in", _F, k)
+    with on_device_of(x) as st:
+        _lib.check(_lib.lib().epnet_sa_tail_f32(b, k, c, p, s, px, pw, pb, ps, pt, int(bool(relu_in)), py, st), "sa_tail_f32")
+    return 1

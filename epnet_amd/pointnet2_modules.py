@@ -6,7 +6,9 @@ reference's pointnet2_lib/pointnet2/pointnet2_modules.py (``_PointnetSAModuleBas
 ``Pointnet2MSG`` / ``RCNNNet`` build on it unchanged and reference checkpoints load. The geometry
 ops (FPS, gather, ball query, grouping, three_nn, three_interpolate) and the neighbourhood max-pool run on
 the HIP kernels; the shared MLPs stay on stock PyTorch-ROCm, the first 1x1 convolution of a level being applied to
-the N points before the grouping instead of to the npoint * nsample grouped columns after it.
+the N points before the grouping instead of to the npoint * nsample grouped columns after it. For inference, ``fused_tail=True``
+ends every scale in one kernel: the last convolution with its batch norm folded in, the ReLU and the max-pool
+(``pointnet2_utils.sa_tail``, float32 only); the default is the stock lines.
 """
 import os
 from typing import List, Optional
@@ -41,8 +43,15 @@ def _foldable(grouper, mlp, features) -> bool:
 
 
 class _PointnetSAModuleBase(nn.Module):
-    def __init__(self):
+    # inference only, opt-in: the last convolution, batch norm, ReLU and max-pool of every scale from one kernel
+    # (pointnet2_utils.sa_tail), where _fused_tail_for says it applies; everything else takes the stock lines
+    fused_tail = False
+
+    def __init__(self, fused_tail: bool = False):
         super().__init__()
+        if fused_tail:
+            self.fused_tail = True
+        self._tail_packs = {}   # scale -> SATail, or None where the mlp cannot be packed; dropped by train() / load_state_dict
         self.npoint = None
         self.groupers = None
         self.mlps = None
@@ -60,6 +69,44 @@ class _PointnetSAModuleBase(nn.Module):
         if self.pool_method == 'avg_pool':
             return F.avg_pool2d(x, kernel_size=window)
         raise NotImplementedError
+
+    def train(self, mode: bool = True):
+        self._tail_packs.clear()
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._tail_packs.clear()
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _fused_tail_for(self, k: int, mlp):
+        """the packed tail of scale k if the fused tail may stand for the end of `mlp` in this call, else None. The pack is
+        cached per scale; it is rebuilt when a tensor it was folded from has been written or replaced since."""
+        if not self.fused_tail or self.training or self.pool_method != 'max_pool':
+            return None
+        if torch.is_grad_enabled() and any(p.requires_grad for p in mlp.parameters()):
+            return None
+        pack = self._tail_packs.get(k, False)
+        if pack is False or (pack is not None and pack.stamp != pointnet2_utils._tail_stamp(mlp)):
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("fused_tail: run one eager forward before capturing a graph (the weights are folded then)")
+            pack = self._tail_packs[k] = pointnet2_utils.pack_sa_tail(mlp)
+        return pack
+
+    def _finish(self, k: int, mlp, hidden: torch.Tensor, layers) -> torch.Tensor:
+        """`layers` (what is left of the flattened mlp) and the pool on `hidden`; with fused_tail, the end of it from
+        pointnet2_utils.sa_tail on the pre-activation of the unit before the last"""
+        pack = self._fused_tail_for(k, mlp)
+        head = len(layers) - pack.replaced if pack is not None else len(layers)
+        for layer in layers[:head]:
+            hidden = layer(hidden)
+        if head < len(layers):
+            if (hidden.is_cuda and hidden.dtype == torch.float32 and hidden.dim() == 4 and hidden.size(3) > 0
+                    and pointnet2_utils.sa_tail_supports(hidden.size(3)) and pack.w.device == hidden.device
+                    and not (torch.is_grad_enabled() and hidden.requires_grad)):
+                return pointnet2_utils.sa_tail(hidden, pack)
+            for layer in layers[head:]:
+                hidden = layer(hidden)
+        return self._pool(hidden).squeeze(-1)
 
     def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor] = None, new_xyz=None, presampled=None):
         """xyz (B,N,3), features (B,C,N) -> (new_xyz (B,npoint,3), new_features (B,sum mlp[-1],npoint),
@@ -107,6 +154,10 @@ class _PointnetSAModuleBase(nn.Module):
                 w = conv.weight[:, :, 0, 0]
                 z = torch.matmul(w[:, 3:], features)            # (B, C_out, N)
                 hidden = pointnet2_utils.group_linear(xyz, new_xyz, z, nidx, w[:, :3], conv.bias)
+                if self.fused_tail:
+                    flat = [layer for unit in mlp.children() for layer in unit.children()]
+                    pooled.append(self._finish(k, mlp, hidden, flat[1:]))   # flat[0] is the folded convolution
+                    continue
                 for name, layer in mlp[0].named_children():     # what follows the convolution inside the first unit
                     if layer is not conv:
                         hidden = layer(hidden)
@@ -120,6 +171,9 @@ class _PointnetSAModuleBase(nn.Module):
                 grouped = grouper(xyz, new_xyz, features, index, idxs[k])
             else:
                 grouped = grouper(xyz, new_xyz, features, index) if index is not None else grouper(xyz, new_xyz, features)
+            if self.fused_tail:
+                pooled.append(self._finish(k, mlp, grouped, [layer for unit in mlp.children() for layer in unit.children()]))
+                continue
             pooled.append(self._pool(mlp(grouped)).squeeze(-1))  # (B, mlp[-1], npoint)
         return new_xyz, torch.cat(pooled, dim=1), idx
 
@@ -128,8 +182,8 @@ class PointnetSAModuleMSG(_PointnetSAModuleBase):
     """multi-scale grouping SA layer"""
 
     def __init__(self, *, npoint: int, radii: List[float], nsamples: List[int], mlps: List[List[int]],
-                 bn: bool = True, use_xyz: bool = True, pool_method='max_pool', instance_norm=False):
-        super().__init__()
+                 bn: bool = True, use_xyz: bool = True, pool_method='max_pool', instance_norm=False, fused_tail: bool = False):
+        super().__init__(fused_tail=fused_tail)
         assert len(radii) == len(nsamples) == len(mlps)
         self.npoint = npoint
         self.pool_method = pool_method
@@ -147,9 +201,9 @@ class PointnetSAModule(PointnetSAModuleMSG):
     """single-scale SA layer (npoint=None -> GroupAll)"""
 
     def __init__(self, *, mlp: List[int], npoint: int = None, radius: float = None, nsample: int = None,
-                 bn: bool = True, use_xyz: bool = True, pool_method='max_pool', instance_norm=False):
+                 bn: bool = True, use_xyz: bool = True, pool_method='max_pool', instance_norm=False, fused_tail: bool = False):
         super().__init__(mlps=[mlp], npoint=npoint, radii=[radius], nsamples=[nsample], bn=bn, use_xyz=use_xyz,
-                         pool_method=pool_method, instance_norm=instance_norm)
+                         pool_method=pool_method, instance_norm=instance_norm, fused_tail=fused_tail)
 
 
 class PointnetFPModule(nn.Module):

@@ -547,3 +547,107 @@ class GroupAll(nn.Module):
             return all_xyz
         all_feat = features.unsqueeze(2)
         return torch.cat([all_xyz, all_feat], dim=1) if self.use_xyz else all_feat
+
+
+# ---- the fused tail of an SA level's shared MLP (inference) ----
+
+def sa_tail_supports(nsample: int) -> bool:
+    """window sizes epnet_sa_tail_f32 takes (include/epnet_ops.h)"""
+    return nsample in (1, 2, 4, 8, 16) or (nsample >= 32 and nsample % 32 == 0)
+
+
+class SATail:
+    """the last unit of a shared MLP with its batch norm folded into the weights (w (C,K), b (C)), and what is left of the
+    unit before it behind its convolution: that unit's batch norm as s_in, t_in (K) or None, and its ReLU (relu_in).
+    `replaced`: how many layers of the flattened mlp the tail stands for."""
+
+    __slots__ = ("w", "b", "s_in", "t_in", "relu_in", "replaced", "stamp")
+
+    def __init__(self, w, b, s_in, t_in, relu_in, replaced, stamp):
+        self.w, self.b, self.s_in, self.t_in, self.relu_in, self.replaced, self.stamp = w, b, s_in, t_in, relu_in, replaced, stamp
+
+
+def _plain_bn(layer) -> Optional[nn.BatchNorm2d]:
+    """the BatchNorm2d of `layer` -- itself, or the only child of pytorch_utils' wrapper -- if it normalises with running
+    statistics; else None"""
+    if isinstance(layer, nn.Sequential) and len(layer) == 1:
+        layer = layer[0]
+    if type(layer) is not nn.BatchNorm2d or not layer.track_running_stats or layer.running_mean is None:
+        return None
+    return layer
+
+
+def _conv_bn_relu(unit):
+    """(conv, bn or None) of a unit that is exactly conv -> [BatchNorm2d ->] ReLU, else None"""
+    if not isinstance(unit, nn.Module):
+        return None
+    layers = list(unit.children())
+    if len(layers) not in (2, 3) or not isinstance(layers[0], nn.Conv2d) or type(layers[-1]) is not nn.ReLU:
+        return None
+    bn = None
+    if len(layers) == 3:
+        bn = _plain_bn(layers[1])
+        if bn is None:
+            return None
+    return layers[0], bn
+
+
+def _bn_affine(bn: nn.BatchNorm2d):
+    """float64 (scale, shift) of an eval-mode batch norm: s = gamma / sqrt(var + eps), t = beta - mean * s"""
+    var, mean = bn.running_var.detach().double(), bn.running_mean.detach().double()
+    s = 1.0 / torch.sqrt(var + bn.eps)
+    if bn.weight is not None:
+        s = bn.weight.detach().double() * s
+    t = -mean * s
+    if bn.bias is not None:
+        t = bn.bias.detach().double() + t
+    return s, t
+
+
+def _tail_sources(mlp):
+    units = list(mlp.children())
+    return [t for unit in units[-2:] for t in list(unit.parameters()) + list(unit.buffers())]
+
+
+def _tail_stamp(mlp):
+    return tuple((t.data_ptr(), t._version) for t in _tail_sources(mlp))
+
+
+def pack_sa_tail(mlp) -> Optional[SATail]:
+    """Folds the last unit of `mlp` for sa_tail. None unless the mlp has at least two units, the last one is
+    conv (1x1, stride 1, groups 1) -> [BatchNorm2d ->] ReLU and the one before it ends in [BatchNorm2d ->] ReLU behind a
+    leading convolution (no instance norm, no pre-activated unit). The batch-norm scale is computed in float64 and
+    W * s, beta - mean * s (+ bias * s), s_in and t_in are rounded to float32 once."""
+    units = list(mlp.children()) if isinstance(mlp, nn.Module) else []
+    if len(units) < 2:
+        return None
+    last, prev = _conv_bn_relu(units[-1]), _conv_bn_relu(units[-2])
+    if last is None or prev is None:
+        return None
+    conv, bn = last
+    if (conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or conv.dilation != (1, 1)
+            or conv.groups != 1 or conv.padding_mode != "zeros"):
+        return None
+    w = conv.weight.detach()[:, :, 0, 0].double()
+    b = conv.bias.detach().double() if conv.bias is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
+    if bn is not None:
+        s, t = _bn_affine(bn)
+        w, b = w * s[:, None], b * s + t
+    s_in = t_in = None
+    if prev[1] is not None:
+        s_in, t_in = (v.float().contiguous() for v in _bn_affine(prev[1]))
+    replaced = len(list(units[-2].children())) - 1 + len(list(units[-1].children()))
+    return SATail(w.float().contiguous(), b.float().contiguous(), s_in, t_in, True, replaced, _tail_stamp(mlp))
+
+
+def sa_tail(x: torch.Tensor, packed: SATail) -> torch.Tensor:
+    """x (B,K,P,S) float32 on the GPU: the pre-activation the convolution of the unit before the last wrote -> (B,C,P), the
+    level's pooled output, from one kernel (epnet_sa_tail_f32). Inference only: no autograd graph is recorded."""
+    b, k, p, s = x.shape
+    c = packed.w.shape[0]
+    if packed.w.shape[1] != k:
+        raise RuntimeError("sa_tail: x has %d channels, the packed weights take %d" % (k, packed.w.shape[1]))
+    x = x.detach().contiguous()
+    y = _new(x, (b, c, p))
+    _ext.sa_tail_wrapper(b, k, c, p, s, x, packed.w, packed.b, packed.s_in, packed.t_in, packed.relu_in, y)
+    return y

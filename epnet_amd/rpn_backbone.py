@@ -20,6 +20,10 @@ It is taken only in eval mode, on the GPU, on float32 maps (not under autocast),
 gradient is needed; in every other case "points" runs exactly the dense lines. ``image_head_rows16=True`` (default False)
 lifts the autocast exclusion: under ``torch.autocast`` with maps that are all of the autocast type, the same conditions take
 the 16-bit MFMA form of the head (its rule rounds the weights and the deconvolutions' result to that type).
+
+``sa_tail``: "stock" (default), or "fused" = ``fused_tail=True`` on all four SA levels: in eval mode without gradients, on
+float32 tensors, every scale's last convolution, batch norm, ReLU and max-pool come from one kernel
+(``pointnet2_utils.sa_tail``); in every other case the stock lines run.
 """
 from dataclasses import dataclass, field
 from typing import List
@@ -140,13 +144,14 @@ def stock_feature_gather(feature_map, xy):
 
 class Pointnet2MSG(nn.Module):
     def __init__(self, input_channels=0, use_xyz=True, config: BackboneConfig = None, sampler="hip", scale=1, pyramid=True,
-                 image_head="dense", image_head_rows16=False):
+                 image_head="dense", image_head_rows16=False, sa_tail="stock"):
         """scale > 1 divides the pyramid's point counts (small test configurations); pyramid: sample all levels up front on
-        a side stream (pointnet2_utils.sample_pyramid); image_head, image_head_rows16: see the module's docstring"""
+        a side stream (pointnet2_utils.sample_pyramid); image_head, image_head_rows16, sa_tail: see the module's docstring"""
         super().__init__()
         cfg = self.cfg = config or BackboneConfig()
         assert sampler in ("hip", "stock")
-        assert image_head in ("dense", "points")
+        assert image_head in ("dense", "points") and sa_tail in ("stock", "fused")
+        self.sa_tail = sa_tail
         self.sampler, self.pyramid, self.image_head = sampler, pyramid, image_head
         self.image_head_rows16 = bool(image_head_rows16)
         self._packed_head = None                   # li_fusion.pack_image_head's result: a cache, not part of the state_dict
@@ -155,7 +160,8 @@ class Pointnet2MSG(nn.Module):
         for k in range(len(cfg.npoints)):
             specs = [[channel_in] + list(m) for m in cfg.mlps[k]]
             self.SA_modules.append(PointnetSAModuleMSG(npoint=cfg.npoints[k] // scale, radii=cfg.radius[k], nsamples=cfg.nsample[k],
-                                                       mlps=specs, use_xyz=use_xyz, bn=cfg.use_bn))
+                                                       mlps=specs, use_xyz=use_xyz, bn=cfg.use_bn,
+                                                       fused_tail=sa_tail == "fused"))
             channel_in = sum(m[-1] for m in cfg.mlps[k])
             skips.append(channel_in)
         if cfg.li_fusion:

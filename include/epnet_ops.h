@@ -1048,6 +1048,25 @@ int epnet_image_head_points_h(int b, int n, int h, int w, int levels, const int 
                               const float *shift, const float *xy, int align_corners, void *out, void *workspace,
                               size_t workspace_bytes, epnet_stream_t stream);
 
+/* The tail of an SA level's shared MLP for inference: the last 1x1 convolution with its batch norm
+ * folded into the weights, the ReLU and the max-pool over the nsample axis in one kernel; the (b, c, p, s) activation is never
+ * written.
+ *   x (b, k, p, s) fp32 contiguous: the hidden tensor, or the pre-activation of the previous convolution together with
+ *     s_in, t_in (k) (both or neither; the previous unit's folded batch norm) and relu_in != 0 (its ReLU)
+ *   w (c, k) with the batch-norm scale folded in, bias (c) or NULL (= zeros), y (b, c, p)
+ * The rule, float32, bit for bit (-0 and +0 counted as equal):
+ *   x'[k]      = fmaf(x[k], s_in[k], t_in[k]) when s_in is given, then max(x', 0) when relu_in is set (a NaN stays a NaN)
+ *   a[c, p, s] = ONE fmaf chain over k = 0 .. k-1 ascending, started from +0: acc = fmaf(w[c, k], x'[k, p, s], acc)
+ *   y[c, p]    = max(max_s a[c, p, s] + bias[c], 0); a NaN anywhere in the window gives NaN, as epnet_pool_max does
+ * (v_mfma_f32_32x32x2_f32 walked over k in order into one accumulator is that chain: no split-K.) No float atomics: an output
+ * depends on its own window and the weights alone. One launch, no host synchronisation, no allocation; records into a HIP
+ * graph. Every pointer may sit at any 4-byte aligned address.
+ * s in {1, 2, 4, 8, 16} or a multiple of 32, p * s < 2^31, k * c < 2^31, at most 2^31 - 1 workgroups, else EPNET_ELIMIT before any launch; a NULL
+ * required pointer, one of s_in / t_in without the other, k < 1 or c < 1: EPNET_EINVAL; b == 0 or p == 0 returns EPNET_OK and
+ * writes nothing. PRECONDITION: y does not alias an input. */
+int epnet_sa_tail_f32(int b, int k, int c, int p, int s, const float *x, const float *w, const float *bias, const float *s_in,
+                      const float *t_in, int relu_in, float *y, epnet_stream_t stream);
+
 /* Host-memory ops: these are CPU ops in the reference itself (called from DataLoader worker
  * processes, lib/datasets/kitti_rcnn_dataset.py:672,767,811,1029,1157), not a fallback.
  * pts_in_boxes3d_cpu, roipool3d.cpp:97-125: pts (N,3), boxes3d (M,7) -> pts_flag (M,N) i64 */
